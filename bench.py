@@ -1,11 +1,21 @@
 #!/usr/bin/env python3
 """bench.py - focused SAR frames/sec + HBM GB/s of the range FFT+phase pass.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 16384] [--stack multilook|magnitude]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 16384] [--dump-outputs DIR] [--full [--stack multilook|magnitude]]
 
 One step = one CSA focus (azimuth FFT+Phi1, range FFT+Phi2+IFFT+Phi3, azimuth IFFT) of one 16384x16384 complex64
 frame whose echo is already resident in HBM (synthetic complex Gaussian noise generated on the device): BASELINE.json
 config 4, the configuration the metric is quoted on.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with the roofline of the range launch inside
+the timed steps).  --full adds every other leg after the timed steps, as before: the one-frame-in-flight steps, every pass
+alone, the batch64 blocks, BASELINE configs 2 and 3, the CPU baselines and the parity figure of the timed frame.
+
+--dump-outputs DIR writes what the last timed step computed, for comparing two builds output for output (the inputs are
+seeded, so the same arguments give the same inputs): DIR/image_rows.npy, a fixed seeded sample of rows of rank 0's
+[n_az x n_rg] complex64 image (columns of the img.T a caller receives) as float32 [rows, n_rg, 2] (re, im), at most
+32 MiB; DIR/image_row_index.npy, their row numbers (float64); at N > 1 also DIR/multilook_slot.npy, rank 0's 16x16
+multilook stack slot of that step (float32).
 
 --gpus N > 1: one process per GPU.  Started bare (`python bench.py --gpus N`, WORLD_SIZE unset) this file spawns the N
 ranks itself as fresh child processes (`python -m torch.distributed.run ... bench.py ...`) BEFORE anything touches the
@@ -14,8 +24,8 @@ the ranks (RANK / LOCAL_RANK / WORLD_SIZE from the environment).  `--gpus` disag
 never a silent 1-GPU run.  At N > 1 frames shard one per rank per step (weak scaling) and each step's frame is
 multilooked 16x16 into its VideoSAR stack slot and all-gathered with RCCL on a second stream.
 
-Every line also carries a `batch64` block: BASELINE.json config 5, the 64-frame VideoSAR batch of two-channel 8192^2
-scenes, frame f -> rank f mod N, strong scaling (sarx.batch.TwoChannelBatch, the driver the tests run too).
+With --full the line also carries a `batch64` block: BASELINE.json config 5, the 64-frame VideoSAR batch of two-channel
+8192^2 scenes, frame f -> rank f mod N, strong scaling (sarx.batch.TwoChannelBatch, the driver the tests run too).
 
 torch is used only for the gloo rendezvous/barrier; the GPU path is libsarx through ctypes.
 """
@@ -35,6 +45,8 @@ for _p in (ROOT, os.path.join(ROOT, "nis-sar-amtigmti-video_amd")):
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s measured float4 copy)
 XGMI_LINK_GBS = 153.0          # one xGMI link, per direction (7 links per GPU, point to point)
 LOOKS = 16
+DUMP_IMAGE_BYTES = 32 << 20    # --dump-outputs: complex64 image rows written at most
+DUMP_SEED = 20240611           # --dump-outputs: which rows (fixed, so two runs sample the same ones)
 
 
 def parse_args(argv=None):
@@ -79,7 +91,19 @@ def parse_args(argv=None):
                     help="permit the gloo-through-host-memory fallback even with one GPU per rank (rehearsals only: such a line is not an xGMI measurement)")
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous only: every rank reports (rank, local rank, world) and exits before touching the GPU")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: one frame in flight, every pass alone, the batch64 blocks, BASELINE "
+                         "configs 2 and 3, the CPU baselines and the parity figure (--passes, --no-cpu, --cpu-sample, --no-batch, --batch-*, "
+                         "--stack, --no-configs and --config3-cpu shape these legs); off: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; a seeded sample of rows of the image, see the "
+                         "module docstring)")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 def spawn_ranks(n, argv):
@@ -208,6 +232,26 @@ def cpu_baseline_two_channel(n_full, workers, n_sample):
             "sample": f"two-channel {n_sample}x{n_sample} complex64 noise frame: oracle focus x2 {t_focus:.2f} s ({workers} thread(s) of "
                       f"{os.cpu_count()}) + ATI/DPCA/mask expressions (NumPy, 1 thread) {t_prod:.2f} s" +
                       (f", scaled x{scale:.0f} by sample count to {n_full}x{n_full}" if scale != 1 else ", the full frame")}
+
+
+def dump_outputs(out_dir, ctx, img, n, slot_ptr=None):
+    """--dump-outputs: a fixed seeded sample of rows of the [n x n] complex64 device image `img` (all rows up to DUMP_IMAGE_BYTES)
+    as float32 (re, im) pairs, their row numbers, and the multilook stack slot at `slot_ptr` when the step wrote one."""
+    import numpy as np
+    from sarx import _ffi
+    from sarx.engine import download_block
+    os.makedirs(out_dir, exist_ok=True)
+    n_rows = max(1, min(n, DUMP_IMAGE_BYTES // (8 * n)))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, n_rows, replace=False))
+    sample = np.empty((n_rows, n), dtype=np.complex64)
+    for i, r in enumerate(rows):
+        sample[i] = download_block(ctx, img.ptr, n, int(r), 1, 0, n)[0]
+    np.save(os.path.join(out_dir, "image_rows.npy"), sample.view(np.float32).reshape(n_rows, n, 2))
+    np.save(os.path.join(out_dir, "image_row_index.npy"), rows.astype(np.float64))
+    if slot_ptr is not None:
+        slot = np.empty((n // LOOKS, n // LOOKS), dtype=np.float32)
+        _ffi.check(ctx.lib.sarx_memcpy_d2h(ctx.h, slot.ctypes.data, slot_ptr, slot.nbytes), ctx.h)
+        np.save(os.path.join(out_dir, "multilook_slot.npy"), slot)
 
 
 def run_single_channel(sarx, ctx, n, steps=200, lanes=2):
@@ -525,9 +569,15 @@ def main():
     alg_bytes = 16.0 * n * n * launches            # one c64 read + one c64 write per sample per launch
     achieved = alg_bytes / (rg_ms * 1e-3) / 1e9
 
+    # what the last timed step (s = K - 1, lane (K - 1) % L) computed, before any later leg reuses its buffers
+    if a.dump_outputs and rank == 0:
+        last = (K - 1) % L
+        slot = d_recv.ptr + ((K - 1) & 1) * slot_bytes * world + rank * slot_bytes if d_recv is not None else None
+        dump_outputs(a.dump_outputs, ctx, d_imgs[last], n, slot)
+
     # the same steps with ONE frame in flight (lane 0 only): a frame's own latency, and the range launch with the GPU to itself
     solo = None
-    if L > 1:
+    if a.full and L > 1:
         Ks = min(K, 40)
         for s in range(2):
             step(s, False, lanes=1)
@@ -554,7 +604,7 @@ def main():
 
     # the frame lane 0 focused, for the parity figure of the line: its echo and its image, downloaded once (after every timed region)
     host_frame = None
-    if rank == 0 and world == 1 and not a.no_cpu and not a.cpu_sample:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu and not a.cpu_sample:
         host_frame = (d_ins[0].download(np.complex64, (n, n)), d_imgs[0].download(np.complex64, (n, n)))
 
     probe = d_img.download(np.complex64, (4, n))
@@ -562,7 +612,7 @@ def main():
 
     # every pass alone, after the timed region (HIP events on the ctx stream, 5 launches each)
     per_pass = {}
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         tmp = ctx.alloc(n * n * 8)
         names = {_ffi.PASS_AZ_FFT_PHI1: ("az_fft_phi1", 2), _ffi.PASS_RG_FFT_PHI2: ("rg_fft_phi2", 1),
                  _ffi.PASS_RG_IFFT_PHI3: ("rg_ifft_phi3", 1), _ffi.PASS_RG_FUSED_23: ("rg_fused_fft_phi2_ifft_phi3", 1),
@@ -758,7 +808,7 @@ def main():
     d_stamp.release()
 
     # ---- the other GPU legs, back to back, before any CPU leg (the driver's GPU-busy sampler then sees one busy stretch) ----------
-    if not a.no_batch:
+    if a.full and not a.no_batch:
         stacks = {"both": ("multilook", "magnitude"), "all": ("multilook", "magnitude", "products"),
                   "default": ("multilook", "products")}.get(a.stack, (a.stack,))
         for st in stacks:
@@ -766,14 +816,14 @@ def main():
             if rank == 0:
                 blk["collective"] = collective or "none (one rank)"
                 line["batch64" if st == "multilook" else "batch64_" + st] = blk
-    if rank == 0 and world == 1 and not a.no_configs:
+    if a.full and rank == 0 and world == 1 and not a.no_configs:
         if n != 4096:
             line["config2_4096"] = run_single_channel(sarx, ctx, 4096, steps=200)         # BASELINE config 2
         line["config3_two_channel"] = run_config3(sarx, ctx, a.batch_size, frames=20, cpu=False)   # BASELINE config 3
 
     # ---- CPU legs (rank 0 only; never inside a timed region) ---------------------------------------------------------------------
     if rank == 0:
-        if not a.no_cpu:
+        if a.full and not a.no_cpu:
             if world == 1:
                 mt = min(os.cpu_count() or 1, 32)
                 frame = (host_frame[0], radar.focus_args(n)) if host_frame is not None else None
@@ -805,7 +855,8 @@ def main():
                 # sample, timed AFTER every GPU leg while the other ranks wait at the final barrier - it is not part of any timed region
                 line["cpu_baseline"] = cpu_baseline(n, workers=1, scaled=True)
                 line["cpu_baseline"]["sample"] += f"; timed on rank 0 of {world} after the GPU legs, the other ranks idle at the barrier"
-        line["leg_order"] = "GPU legs back to back first (headline, one frame in flight, passes, batch64 blocks, configs 2 and 3), CPU legs last"
+        line["leg_order"] = ("GPU legs back to back first (headline, one frame in flight, passes, batch64 blocks, configs 2 and 3), CPU legs last"
+                             if a.full else "headline steps only (--full adds the other legs)")
         emit(line)
     if dist is not None:
         dist.barrier()
