@@ -1,9 +1,11 @@
 // libsarx C ABI (include/sarx.h): context, CSA plan (fp64 migration tables,
 // twiddles, scratch), pass orchestration, ATI/DPCA, RCCL all-gather.
 #include "../../include/sarx.h"
+#include "../../include/sarx_gmti.h"
 #include "csa_kernels.h"
 #include "general.h"
 #include "tdbp.h"
+#include "gmti.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -139,6 +141,8 @@ struct sarx_ctx {
     int n_ranks = 0, rank = 0;
     int range_cus = 0;                 // > 0: persistent range launches size their grid for this many CUs (sarx_set_range_cus; frames in flight)
     int range_impl = 0;                // SARX_RANGE_IMPL: 0 auto, 1 = 16 pts/thread, 2 = 32 pts/thread split exchange, 3 = fused wave-private, 4 = sixteen-wave permuted-spectrum pair
+    sarx_gmti_report* gmti_copy[LANES] = {};   // sarx_gmti_refine_dev: the unordered list it sorts from, one per lane
+    size_t gmti_copy_cap[LANES] = {};          // reports it holds
     std::string err;
 };
 
@@ -406,6 +410,7 @@ int sarx_destroy(sarx_ctx* c) {
     hipSetDevice(c->device);
     hipDeviceSynchronize();
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
+    for (int k = 0; k < sarx_ctx::LANES; ++k) hipFree(c->gmti_copy[k]);
     hipFree(c->tw_all); hipFree(c->ati_part_max_all); hipFree(c->ati_part_sum_all); hipFree(c->ati_out3_all); hipFree(c->power_part_all);
     for (int i = 0; i < N_EVENTS; ++i) hipEventDestroy(c->ev[i]);
     hipEventDestroy(c->comm_fence);
@@ -1587,6 +1592,70 @@ int sarx_comm_wait_mark(sarx_ctx* c, int slot) {
 int sarx_comm_destroy(sarx_ctx* c) {
     NEED_CTX(c);
     if (c->comm) { hipStreamSynchronize(c->comm_stream); g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
+    return SARX_OK;
+}
+
+// ---- GMTI detection (include/sarx_gmti.h, gmti.hip) ---------------------------------------------------------------------------
+static int gmti_check_params(sarx_ctx* c, const sarx_gmti_params* p) {
+    if (!p) return fail(c, SARX_ERR_INVALID, "GMTI params is NULL");
+    if (p->guard_az < 0 || p->guard_rg < 0 || p->train_az < 0 || p->train_rg < 0)
+        return fail(c, SARX_ERR_INVALID, "GMTI half-widths must be >= 0 (guard %d x %d, train %d x %d)", p->guard_az, p->guard_rg,
+                    p->train_az, p->train_rg);
+    if (p->guard_az + p->train_az > SARX_GMTI_MAX_HALF || p->guard_rg + p->train_rg > SARX_GMTI_MAX_HALF)
+        return fail(c, SARX_ERR_UNSUPPORTED, "GMTI guard + train half-widths %d x %d exceed %d", p->guard_az + p->train_az,
+                    p->guard_rg + p->train_rg, SARX_GMTI_MAX_HALF);
+    if (p->train_az == 0 && p->train_rg == 0) return fail(c, SARX_ERR_INVALID, "GMTI training set is empty (train half-widths 0 x 0)");
+    if (!(p->alpha > 0.0) || !std::isfinite(p->alpha)) return fail(c, SARX_ERR_INVALID, "GMTI alpha must be finite and > 0");
+    if (p->min_train < 1) return fail(c, SARX_ERR_INVALID, "GMTI min_train must be >= 1");
+    if (p->max_detections < 1) return fail(c, SARX_ERR_INVALID, "GMTI max_detections must be >= 1");
+    return SARX_OK;
+}
+
+int sarx_gmti_slot_bytes(const sarx_gmti_params* p, size_t* out) {
+    if (!out) return fail(nullptr, SARX_ERR_INVALID, "out_bytes is NULL");
+    const int rc = gmti_check_params(nullptr, p);
+    if (rc != SARX_OK) return rc;
+    *out = sizeof(sarx_gmti_header) + (size_t)p->max_detections * sizeof(sarx_gmti_report);
+    return SARX_OK;
+}
+
+int sarx_gmti_cfar_dev(sarx_ctx* c, const float* d_mag, int n_az, int n_rg, const sarx_gmti_params* p, sarx_gmti_report* d_reports,
+                       sarx_gmti_header* d_header) {
+    NEED_CTX(c);
+    const int rc = gmti_check_params(c, p);
+    if (rc != SARX_OK) return rc;
+    if (!d_mag || !d_reports || !d_header) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
+    if (n_az < 1 || n_rg < 1) return fail(c, SARX_ERR_INVALID, "bad plane size %d x %d", n_az, n_rg);
+    if (((uintptr_t)d_reports & 7) || ((uintptr_t)d_header & 3)) return fail(c, SARX_ERR_INVALID, "misaligned report list or header");
+    GmtiCfarArgs a{};
+    a.m = d_mag; a.n_az = n_az; a.n_rg = n_rg;
+    a.ga = p->guard_az; a.gr = p->guard_rg; a.oa = p->guard_az + p->train_az; a.orr = p->guard_rg + p->train_rg;
+    a.alpha = p->alpha; a.min_train = p->min_train; a.max_det = p->max_detections;
+    a.rep = d_reports; a.hdr = d_header;
+    HIPCHK(c, launch_gmti_cfar(a, c->stream));
+    return SARX_OK;
+}
+
+int sarx_gmti_refine_dev(sarx_ctx* c, const void* d_slc1, const void* d_slc2, int n_az, int n_rg, double cal_phase,
+                         sarx_gmti_report* d_reports, const sarx_gmti_header* d_header, int max_det) {
+    NEED_CTX(c);
+    if (!d_slc1 || !d_slc2 || !d_reports || !d_header) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
+    if (n_az < 1 || n_rg < 1) return fail(c, SARX_ERR_INVALID, "bad image size %d x %d", n_az, n_rg);
+    if (max_det < 1) return fail(c, SARX_ERR_INVALID, "max_detections must be >= 1");
+    if (!std::isfinite(cal_phase)) return fail(c, SARX_ERR_INVALID, "cal_phase is not finite");
+    if (((uintptr_t)d_reports & 7) || ((uintptr_t)d_header & 3)) return fail(c, SARX_ERR_INVALID, "misaligned report list or header");
+    const int L = c->cur_lane;
+    if (c->gmti_copy_cap[L] < (size_t)max_det) {         // grows only; a frame loop allocates once per lane
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipFree(c->gmti_copy[L]));
+        c->gmti_copy[L] = nullptr;
+        c->gmti_copy_cap[L] = 0;
+        HIPCHK(c, hipMalloc((void**)&c->gmti_copy[L], (size_t)max_det * sizeof(sarx_gmti_report)));
+        c->gmti_copy_cap[L] = (size_t)max_det;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->gmti_copy[L], d_reports, (size_t)max_det * sizeof(sarx_gmti_report), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, launch_gmti_refine((const float2*)d_slc1, (const float2*)d_slc2, n_az, n_rg, cal_phase, c->gmti_copy[L], d_reports, d_header,
+                                 max_det, c->stream));
     return SARX_OK;
 }
 

@@ -134,6 +134,32 @@ SIGNATURES = {
     "sarx_comm_destroy": (_i, [_vp]),
 }
 
+# include/sarx_gmti.h: the GMTI detector's structs and entry points, bound by load() beside SIGNATURES (a table of its own: sarx.h
+# and SIGNATURES stay exactly what they are)
+class GmtiParams(C.Structure):
+    """sarx_gmti_params"""
+    _fields_ = [("guard_az", C.c_int32), ("guard_rg", C.c_int32), ("train_az", C.c_int32), ("train_rg", C.c_int32),
+                ("alpha", C.c_double), ("min_train", C.c_int32), ("max_detections", C.c_int32)]
+
+
+class GmtiHeader(C.Structure):
+    """sarx_gmti_header: the first 16 bytes of a detection slot"""
+    _fields_ = [("count", C.c_uint32), ("overflow", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class GmtiReport(C.Structure):
+    """sarx_gmti_report (48 bytes)"""
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("power", C.c_double), ("mean", C.c_double), ("interf_re", C.c_double),
+                ("interf_im", C.c_double), ("mag1", C.c_float), ("mag2", C.c_float)]
+
+
+GMTI_MAX_HALF = 32              # SARX_GMTI_MAX_HALF
+GMTI_SIGNATURES = {
+    "sarx_gmti_slot_bytes": (_i, [_P(GmtiParams), _P(_sz)]),
+    "sarx_gmti_cfar_dev": (_i, [_vp, _vp, _i, _i, _P(GmtiParams), _vp, _vp]),
+    "sarx_gmti_refine_dev": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _i]),
+}
+
 _lib = None
 
 
@@ -146,7 +172,7 @@ def load():
         raise SarxError(-3, f"{LIB_PATH} not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
                             "or `make -C nis-sar-amtigmti-video_amd/csrc` (hipcc, gfx950). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

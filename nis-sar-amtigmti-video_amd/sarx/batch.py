@@ -185,7 +185,7 @@ def run_batch_host(frame_ids_all, world, rank, process_frame, comm, slot_shape=N
 # ----------------------------------------------------------------------------------------------------------------
 # BASELINE config 5 on the device: a VideoSAR batch of two-channel scenes, frame f -> rank f mod N
 # ----------------------------------------------------------------------------------------------------------------
-STACKS = ("multilook", "magnitude", "products")
+STACKS = ("multilook", "magnitude", "products", "detections")
 
 
 class _Ptr:
@@ -206,7 +206,11 @@ class TwoChannelBatch:
     resolution (256 MiB per 8192^2 frame: the configuration that loads xGMI);  stack="products": the frame's three GMTI
     planes [masked ATI phase, |slc1|, DPCA magnitude] (:414-419,447-449; 768 MiB per 8192^2 frame - SURVEY.md 8(e)'s
     [frames x 3 x n x n] product stack), written by channel 2's last azimuth launch straight at their place in the
-    stack buffer, so the per-frame products leave the GPU they were computed on instead of being overwritten.
+    stack buffer, so the per-frame products leave the GPU they were computed on instead of being overwritten;
+    stack="detections": the GMTI report list of the frame (sarx.gmti: CFAR on the DPCA plane, refined with both images), a
+    fixed-size block of header (count, overflow flag) + `detect.max_detections` reports written by the detector straight at
+    the frame's place in the stack buffer (196 KiB per frame at the default 4096 reports, whatever the frame size);
+    b.detections(f) decodes it.
 
     The stack lives in one device buffer [rounds][world][slot]; a frame's slot is produced directly at its place
     and each round is gathered IN PLACE (send = recv + rank * slot), so there is no send buffer to recycle and no
@@ -218,7 +222,7 @@ class TwoChannelBatch:
 
     def __init__(self, ctx, n, n_frames, world=1, rank=0, stack="multilook", looks=16, rccl=False, host_comm=None,
                  seed_base=1000, flags=None, mask_frac=0.05, resident=True, fused_mask=True, fused_ati=True, scene="noise",
-                 scene_scale=1.0, lanes=None):
+                 scene_scale=1.0, lanes=None, detect=None):
         from . import _ffi, radar
         from .engine import CsaPlan
         if stack not in STACKS:
@@ -265,7 +269,13 @@ class TwoChannelBatch:
         # ... and the ATI / DPCA products out of channel 2's last azimuth launch (sarx_csa_plan_set_ati): slc2 is never written,
         # neither image is read again; sizes without that epilogue keep the separate launch
         self.fused_ati = bool(fused_ati) and self.fused_mask and n % 64 == 0
-        self.slot_shape = (n // looks, n // looks) if stack == "multilook" else (n, n) if stack == "magnitude" else (3, n, n)
+        if stack == "detections":
+            from .gmti import GmtiParams
+            self.detect = detect if detect is not None else GmtiParams()
+            self.slot_shape = (self.detect.slot_bytes() // 4,)       # raw bytes, carried as fp32 words by every transport
+        else:
+            self.detect = None
+            self.slot_shape = (n // looks, n // looks) if stack == "multilook" else (n, n) if stack == "magnitude" else (3, n, n)
         self.slot_bytes = int(np.prod(self.slot_shape)) * 4
         self.n_rounds = rounds(self.n_frames, self.world)
         self.mine = shard_frames(self.n_frames, self.world, self.rank)
@@ -351,9 +361,11 @@ class TwoChannelBatch:
                 mag = _Ptr(slot_ptr)
             elif self._slot_written:                       # the three planes of the frame, in place in the stack
                 masked, mag, dm = (_Ptr(slot_ptr + i * self.px * 4) for i in range(3))
-            self.plan.set_ati(self.s1, self.d_max, self.mask_frac, 0.0, masked, mag, dm)
-            self.plan.focus_dev(bufs[1], self.s2)               # s2 serves as scratch only
+            # s2 serves as scratch only - unless the detector's refine launch reads it
+            self.plan.set_ati(self.s1, self.d_max, self.mask_frac, 0.0, masked, mag, dm, keep_image=self.detect is not None)
+            self.plan.focus_dev(bufs[1], self.s2)
             self.plan.set_ati(None)
+            self._detect(dm, slot_ptr)
             return
         self.plan.focus_dev(bufs[1], self.s2)
         self._slot_written = False
@@ -368,6 +380,28 @@ class TwoChannelBatch:
         else:
             ctx.ati_dpca(self.s1, self.s2, self.px, 0.0, outs, want_stats=False)
             ctx.mask_phase_frac(outs["ati_phase"], outs["slc1_mag"], self.px, self.mask_frac, masked)
+        self._detect(outs["dpca_mag"], slot_ptr)
+
+    def _detect(self, dpca_mag, slot_ptr):
+        """stack="detections": the frame's report list into its slot (CFAR + refine on this lane, no host round trip)."""
+        if self.detect is None or slot_ptr is None:
+            return
+        from . import gmti
+        from ._ffi import check
+        check(self.ctx.lib.sarx_memset(self.ctx.h, slot_ptr, 0, self.slot_bytes), self.ctx.h)     # no stale bytes past the count
+        gmti.enqueue(self.ctx, dpca_mag.ptr, self.s1.ptr, self.s2.ptr, self.n, self.n, self.detect, 0.0, slot_ptr)
+
+    def detections(self, f):
+        """stack="detections": frame f's GmtiReport, decoded from the assembled stack (raises GmtiOverflowError if its list
+        overflowed).  Axes and radar from the batch's focus; the lag is one pulse unless detect.lag_s says otherwise."""
+        from . import gmti
+        if self.detect is None:
+            raise ValueError('detections() needs stack="detections"')
+        raw = self.stack([f])[0].view(np.uint8)
+        ra, ca = self._lane_state[0]["plan"].axes()
+        lam, prf, v = self.focus_args[0], self.focus_args[4], self.focus_args[5]
+        lag = self.detect.lag_s if self.detect.lag_s is not None else 1.0 / prf
+        return gmti.decode_slot(raw, self.detect, ra, ca, lam, v, lag)
 
     def _slot_ptr(self, i, r):
         return self.d_stack.ptr + (i * self.world + r) * self.slot_bytes

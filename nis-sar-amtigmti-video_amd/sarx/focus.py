@@ -265,7 +265,7 @@ def two_channel_workspace(ctx, n_az, n_rg):
 def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp_rate_hzpsec, sample_rate_hz,
                    prf_hz, platform_speed_mps, range_ref_m, t_start_fast, mask_frac=0.05, cal_phase=0.0, *,
                    ctx=None, pulse_shift=True, return_slc2=True, unmasked_phase=False, device_output=False,
-                   workspace=None, fetch_stats=True):
+                   workspace=None, fetch_stats=True, detect=None):
     """The reference script's processing section in one call
     (sar_ati_dcpa_sim_csa.py:402-419,447-449): pulse shift, CSA focus of both
     channels, ATI/DPCA products, 5 % magnitude mask.  Nothing visits the host between the steps; with DeviceArray
@@ -287,6 +287,10 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
                           enqueues: no host synchronisation at all; Context.ati_stats() fetches them later)
     workspace           : two_channel_workspace(ctx, N_az, N_rg): buffers reused from call to call (with device_output the
                           returned buffers ARE the workspace's - do not release them per call)
+    detect              : sarx.GmtiParams: the GMTI detector (sarx.gmti_detect) runs on the device planes of this call and
+                          res["detections"] is its GmtiReport (channel 2's image is then kept on the device even with
+                          return_slc2=False, for the refine launch, but not returned); with device_output only the report list
+                          is downloaded
     """
     ctx = ctx or default_context()
     on_device = isinstance(raw_rx1, DeviceArray) and isinstance(raw_rx2, DeviceArray)
@@ -347,7 +351,7 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
             if have_max and not unmasked_phase:
                 try:                                        # channel 2: the products come out of its last azimuth launch
                     plan.set_ati(bufs["slc1"], bufs["d_max"], mask_frac, cal_phase, bufs["ati_phase_masked"], bufs["slc1_mag"],
-                                 bufs["dpca_mag"], keep_image=return_slc2)
+                                 bufs["dpca_mag"], keep_image=return_slc2 or detect is not None)
                     fused = True
                 except _ffi.SarxError:
                     fused = False
@@ -368,9 +372,22 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
             else:                                           # mask inside the ATI launch, threshold from channel 1's focus
                 outs = {"ati_phase": bufs["ati_phase_masked"], "slc1_mag": bufs["slc1_mag"], "dpca_mag": bufs["dpca_mag"]}
                 ctx.ati_dpca_masked(bufs["slc1"], bufs["slc2"], n, cal_phase, bufs["d_max"], mask_frac, outs)
-        max_mag, sum_interf = ctx.ati_stats() if (fetch_stats or not device_output) else (None, None)   # the only host synchronisation of the chain
         ra, ca = plan.axes()
+        report = None
+        if detect is not None:                              # CFAR + refine on the planes of this call; the report list comes back
+            from . import gmti
+            slot = ctx.alloc(detect.slot_bytes())
+            try:
+                gmti.enqueue(ctx, bufs["dpca_mag"].ptr, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, detect, cal_phase, slot.ptr)
+                raw = gmti.fetch_slot(ctx, slot.ptr, detect.max_detections)
+            finally:
+                slot.release()
+            report = gmti.decode_slot(raw, detect, ra, ca, center_wavelength_m, platform_speed_mps,
+                                      detect.lag_s if detect.lag_s is not None else 1.0 / prf_hz)
+        max_mag, sum_interf = ctx.ati_stats() if (fetch_stats or not device_output) else (None, None)   # the only host synchronisation of the chain
         res = {"range_axis": ra, "cross_range": ca, "max_mag": max_mag, "sum_interf": sum_interf, "fused_products": fused}
+        if report is not None:
+            res["detections"] = report
         names = ["slc1"] + (["slc2"] if (return_slc2 or not fused) else []) + ["slc1_mag", "dpca_mag", "ati_phase_masked"] + \
                 (["ati_phase"] if "ati_phase" in bufs else [])
         if device_output:
