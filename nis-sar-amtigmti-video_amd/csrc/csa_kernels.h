@@ -116,6 +116,10 @@ bool range_conv_supported(int m);
 hipError_t launch_range_conv(int m, const RangeArgs& a, int cus, hipStream_t st);
 // r: FFT length of the tile (2..128), w: tile width in range samples (16 or 32), nq: tiles along azimuth
 hipError_t launch_az_tile(int r, int w, bool inv, int epi, const AzArgs& a, int nq, hipStream_t st);
+// az_wave.hip: r = 128 tiles of 32 columns, one wave per tile in registers (no LDS, no barrier), wpb waves per workgroup (1 or 4);
+// epilogues TWIDDLE (both directions), PHI1 (forward), SCALE (inverse, with max_out)
+bool az_wave_supported(int r, int n_rg, int epi, int wpb);
+hipError_t launch_az_wave(bool inv, int epi, int wpb, const AzArgs& a, int nq, hipStream_t st);
 
 // Middle launch of a two-step chirp-z column transform of length M = ra * s (general.hip): tile q holds rows q*s + m
 // (m < s) of a [M x n_rg] array; FFT_s over m gives bins q + ra*k2, times bhat[q + ra*k2] (a.rowvec, natural order),

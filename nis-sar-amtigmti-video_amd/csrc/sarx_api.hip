@@ -157,6 +157,10 @@ struct sarx_plan {
                            // 512-byte row segments at 16384^2, 1.57-1.58 against 1.62-1.66 ms per two-launch transform; with frames in flight
                            // the 64 KiB tiles share CUs worse with the other lane's range launch (4.03-4.09 against 3.99-4.00 ms per frame),
                            // at 8192^2 and below nothing changes (profiles/r05_p_az_tile_width.log)
+    int az_impl = 1;       // SARX_AZ_IMPL: 1 = the 128-point steps of n_az = 16384 (TWIDDLE / PHI1 / SCALE epilogues) run as wave-private
+                           // tiles (az_wave.hip) whatever the tile width, CU share or slab mode; 0 = az_tile_kernel everywhere
+    int az_wpb = 4;        // SARX_AZ_WAVES: waves (independent tiles) per workgroup of those launches, 1 or 4 (4: 0.73-0.75 against
+                           // 0.83-0.84 ms per step alone at 16384^2, profiles/az_wave_steps.jsonl)
     int look = 0;          // > 0: the last azimuth launch also writes row-wise |x|^2 partials and a finish launch turns them into look_slot
     float* look_slot = nullptr;   // caller's [n_az/look x n_rg/look] fp32 slot (device)
     float* look_part = nullptr;   // [n_az x n_rg/look], owned by the plan
@@ -674,6 +678,8 @@ static int sarx_csa_plan_create_impl(sarx_ctx* c, int n_az, int n_rg, const sarx
     }
     if (const char* e = getenv("SARX_AZ_W")) { const int w = atoi(e); if ((w == 16 || w == 32 || w == 64) && n_rg % w == 0) p->az_w = w; }
     else if (n_rg % 64 == 0 && (size_t)n_az * n_rg * sizeof(float2) >= ((size_t)1 << 31)) p->az_w_alone = 64;
+    if (const char* e = getenv("SARX_AZ_IMPL")) p->az_impl = atoi(e) != 0;
+    if (const char* e = getenv("SARX_AZ_WAVES")) { const int w = atoi(e); if (w == 1 || w == 4) p->az_wpb = w; }
 
     // migration factors, natural fftfreq order (sar_ati_dcpa_sim_csa.py:225,244-249,262)
     const double lam = prm->wavelength_m, Kr = prm->chirp_rate_hz_s, Vr = prm->platform_speed_mps, Rref = prm->range_ref_m;
@@ -905,10 +911,13 @@ static int az_step(sarx_plan* p, bool inv, bool step_b, int S, const void* in, v
     a.nt = p->az_nt;
     const bool alone = !(c->range_cus > 0 && c->range_cus < c->cus);
     const int w_plain = (alone && p->az_w_alone) ? p->az_w_alone : p->az_w;      // the same columns' arithmetic either way: bit-identical images
+    // wave-private 128-point tiles: chosen by the plan alone (not by the CU share), so every mode runs the same arithmetic
+    const auto wave = [&](int r, int epi) { return p->az_impl && n == 16384 && az_wave_supported(r, p->n_rg, epi, p->az_wpb); };
     if (!step_b) {
         a.tw_r = c->tw_all + RA;
         a.in_q_stride = 1; a.in_m_stride = S; a.out_q_stride = 1; a.out_m_stride = S;
-        HIPCHK(c, launch_az_tile(RA, w_plain, inv, AZ_EPI_TWIDDLE, a, nq, c->stream));
+        if (wave(RA, AZ_EPI_TWIDDLE)) HIPCHK(c, launch_az_wave(inv, AZ_EPI_TWIDDLE, p->az_wpb, a, nq, c->stream));
+        else HIPCHK(c, launch_az_tile(RA, w_plain, inv, AZ_EPI_TWIDDLE, a, nq, c->stream));
     } else {
         a.tw_r = c->tw_all + S;
         a.in_q_stride = S; a.in_m_stride = 1; a.out_q_stride = 1; a.out_m_stride = RA;
@@ -917,7 +926,9 @@ static int az_step(sarx_plan* p, bool inv, bool step_b, int S, const void* in, v
         const bool ati = inv && p->ati_s1;
         if (inv && !ati) a.max_out = reinterpret_cast<unsigned*>(p->max_slot);      // an armed ATI epilogue reads the slot (ati_thr): never reduce into it then
         if (ati) ati_args(p, a);
-        HIPCHK(c, launch_az_tile(S, ati ? p->ati_w : look ? p->az_w : w_plain, inv, inv ? (ati ? AZ_EPI_SCALE_ATI : look ? AZ_EPI_SCALE_LOOK : AZ_EPI_SCALE) : AZ_EPI_PHI1, a, nq, c->stream));
+        const int epi = inv ? (ati ? AZ_EPI_SCALE_ATI : look ? AZ_EPI_SCALE_LOOK : AZ_EPI_SCALE) : AZ_EPI_PHI1;
+        if (wave(S, epi)) HIPCHK(c, launch_az_wave(inv, epi, p->az_wpb, a, nq, c->stream));
+        else HIPCHK(c, launch_az_tile(S, ati ? p->ati_w : look ? p->az_w : w_plain, inv, epi, a, nq, c->stream));
     }
     return SARX_OK;
 }
@@ -1008,6 +1019,13 @@ int sarx_csa_pass(sarx_plan* p, int pass_id, const void* d_in, void* d_out) {
             RangeArgs a = range_args(p, d_in, d_out);
             HIPCHK(c, launch_range_wp(pass_id == SARX_PASS_RG_FFT_PHI2_PERM ? RG_FFT_PHI2 : RG_IFFT_PHI3, a, c->cus, c->stream));
             return SARX_OK;
+        }
+        case 110: case 111: case 112: case 113: {     // one step of a four-step azimuth transform (tests): forward A, B, inverse A, B
+            if (p->az_s == p->n_az || d_in == d_out || d_in == p->buf_b || d_out == p->buf_b)
+                return fail(c, SARX_ERR_INVALID, "azimuth steps exist for four-step plans and are out-of-place");
+            const bool inv = pass_id >= 112, step_b = pass_id & 1;
+            if (inv && step_b && p->max_slot && !p->ati_s1) HIPCHK(c, hipMemsetAsync(p->max_slot, 0, MAX_SLOT_BYTES, c->stream));
+            return az_step(p, inv, step_b, p->az_s, d_in, d_out, 0, step_b ? p->n_az / p->az_s : p->az_s);
         }
         case 100: { RangeArgs a = range_args(p, d_in, d_out); HIPCHK(c, run_range(p, RG_FFT, a)); return SARX_OK; }   // plain FFT (tests)
         case 101: { RangeArgs a = range_args(p, d_in, d_out); HIPCHK(c, run_range(p, RG_IFFT, a)); return SARX_OK; }  // plain IFFT (tests)
