@@ -160,6 +160,31 @@ GMTI_SIGNATURES = {
     "sarx_gmti_refine_dev": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _i]),
 }
 
+# include/sarx_refocus.h: the GMTI refocus, a third table bound the same way
+REFOCUS_MAX_HYP = 64            # SARX_REFOCUS_MAX_HYP
+REFOCUS_MAX_W = 15              # SARX_REFOCUS_MAX_W
+REFOCUS_DPCA, REFOCUS_SLC1 = 0, 1
+
+
+class RefocusParams(C.Structure):
+    """sarx_refocus_params (576 bytes)"""
+    _fields_ = [("chip_az", C.c_int32), ("chip_rg", C.c_int32), ("source", C.c_int32), ("n_hyp", C.c_int32),
+                ("wavelength_m", C.c_double), ("platform_speed_mps", C.c_double), ("prf_hz", C.c_double), ("r0_m", C.c_double),
+                ("dr_m", C.c_double), ("cal_phase", C.c_double), ("speed_mps", C.c_double * REFOCUS_MAX_HYP)]
+
+
+class RefocusRecord(C.Structure):
+    """sarx_refocus_record (48 bytes)"""
+    _fields_ = [("k_best", C.c_int32), ("i0", C.c_int32), ("peak_i", C.c_int32), ("peak_j", C.c_int32), ("s_prev", C.c_float),
+                ("s_best", C.c_float), ("s_next", C.c_float), ("s_identity", C.c_float), ("peak_power", C.c_float),
+                ("orig_power", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+REFOCUS_SIGNATURES = {
+    "sarx_refocus_check": (_i, [_P(RefocusParams), _i, _i]),
+    "sarx_refocus_dev": (_i, [_vp, _vp, _vp, _i, _i, _P(RefocusParams), _vp, _vp, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -172,7 +197,7 @@ def load():
         raise SarxError(-3, f"{LIB_PATH} not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
                             "or `make -C nis-sar-amtigmti-video_amd/csrc` (hipcc, gfx950). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -222,7 +222,7 @@ class TwoChannelBatch:
 
     def __init__(self, ctx, n, n_frames, world=1, rank=0, stack="multilook", looks=16, rccl=False, host_comm=None,
                  seed_base=1000, flags=None, mask_frac=0.05, resident=True, fused_mask=True, fused_ati=True, scene="noise",
-                 scene_scale=1.0, lanes=None, detect=None):
+                 scene_scale=1.0, lanes=None, detect=None, refocus=None):
         from . import _ffi, radar
         from .engine import CsaPlan
         if stack not in STACKS:
@@ -269,10 +269,22 @@ class TwoChannelBatch:
         # ... and the ATI / DPCA products out of channel 2's last azimuth launch (sarx_csa_plan_set_ati): slc2 is never written,
         # neither image is read again; sizes without that epilogue keep the separate launch
         self.fused_ati = bool(fused_ati) and self.fused_mask and n % 64 == 0
+        self.refocus_params = None
+        if refocus is not None and stack != "detections":
+            raise ValueError('refocus needs stack="detections"')
         if stack == "detections":
             from .gmti import GmtiParams
             self.detect = detect if detect is not None else GmtiParams()
-            self.slot_shape = (self.detect.slot_bytes() // 4,)       # raw bytes, carried as fp32 words by every transport
+            self.gmti_bytes = self.detect.slot_bytes()
+            extra = 0
+            if refocus is not None:                                  # the frame's refocus records ride behind its report list
+                import dataclasses
+                kc = self.k or radar.reference_constants()
+                vg = refocus.footprint_speed_mps if refocus.footprint_speed_mps is not None else kc["V_sat"] * kc["Re"] / kc["R_sat"]
+                self.refocus_params = dataclasses.replace(refocus, footprint_speed_mps=vg, want_curves=False, want_chips=False)
+                self.refocus_params.validate(self.n)
+                extra = self.refocus_params.record_bytes(self.detect.max_detections)
+            self.slot_shape = ((self.gmti_bytes + extra) // 4,)     # raw bytes, carried as fp32 words by every transport
         else:
             self.detect = None
             self.slot_shape = (n // looks, n // looks) if stack == "multilook" else (n, n) if stack == "magnitude" else (3, n, n)
@@ -390,6 +402,13 @@ class TwoChannelBatch:
         from ._ffi import check
         check(self.ctx.lib.sarx_memset(self.ctx.h, slot_ptr, 0, self.slot_bytes), self.ctx.h)     # no stale bytes past the count
         gmti.enqueue(self.ctx, dpca_mag.ptr, self.s1.ptr, self.s2.ptr, self.n, self.n, self.detect, 0.0, slot_ptr)
+        if self.refocus_params is not None:
+            from . import refocus
+            r0, dr = refocus.range_geometry(self.plan.axes()[0])
+            lam, prf, v = self.focus_args[0], self.focus_args[4], self.focus_args[5]
+            cp = self.refocus_params.c_params(lam, v, prf, r0, dr, 0.0)
+            refocus.enqueue(self.ctx, self.s1.ptr, self.s2.ptr, self.n, self.n, cp, slot_ptr, self.detect.max_detections,
+                            slot_ptr + self.gmti_bytes)
 
     def detections(self, f):
         """stack="detections": frame f's GmtiReport, decoded from the assembled stack (raises GmtiOverflowError if its list
@@ -402,6 +421,20 @@ class TwoChannelBatch:
         lam, prf, v = self.focus_args[0], self.focus_args[4], self.focus_args[5]
         lag = self.detect.lag_s if self.detect.lag_s is not None else 1.0 / prf
         return gmti.decode_slot(raw, self.detect, ra, ca, lam, v, lag)
+
+    def refocus(self, f):
+        """stack="detections" with refocus=: frame f's RefocusResult, decoded from the records behind its report list (raises
+        GmtiOverflowError if the list overflowed).  V_r is the batch's focus speed, V_g the orbit's footprint speed."""
+        from . import gmti, refocus
+        if self.refocus_params is None:
+            raise ValueError("refocus() needs refocus=")
+        raw = self.stack([f])[0].view(np.uint8)
+        count, overflow = (int(x) for x in raw[:8].view("<u4"))
+        if overflow or count > self.detect.max_detections:
+            raise gmti.GmtiOverflowError(count, self.detect.max_detections)
+        rep = raw[gmti.HEADER_BYTES:gmti.HEADER_BYTES + count * gmti.REPORT_DTYPE.itemsize].view(gmti.REPORT_DTYPE)
+        rec = raw[self.gmti_bytes:self.gmti_bytes + count * refocus.RECORD_DTYPE.itemsize]
+        return refocus.decode(rec, np.stack([rep["i"], rep["j"]], axis=1), self.refocus_params, self.focus_args[5])
 
     def _slot_ptr(self, i, r):
         return self.d_stack.ptr + (i * self.world + r) * self.slot_bytes

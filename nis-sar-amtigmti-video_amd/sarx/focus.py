@@ -265,7 +265,7 @@ def two_channel_workspace(ctx, n_az, n_rg):
 def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp_rate_hzpsec, sample_rate_hz,
                    prf_hz, platform_speed_mps, range_ref_m, t_start_fast, mask_frac=0.05, cal_phase=0.0, *,
                    ctx=None, pulse_shift=True, return_slc2=True, unmasked_phase=False, device_output=False,
-                   workspace=None, fetch_stats=True, detect=None):
+                   workspace=None, fetch_stats=True, detect=None, refocus=None):
     """The reference script's processing section in one call
     (sar_ati_dcpa_sim_csa.py:402-419,447-449): pulse shift, CSA focus of both
     channels, ATI/DPCA products, 5 % magnitude mask.  Nothing visits the host between the steps; with DeviceArray
@@ -291,7 +291,11 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
                           res["detections"] is its GmtiReport (channel 2's image is then kept on the device even with
                           return_slc2=False, for the refine launch, but not returned); with device_output only the report list
                           is downloaded
+    refocus             : sarx.RefocusParams (needs detect): the GMTI refocus (sarx.gmti_refocus) runs on this call's device
+                          images straight after the detector, on the same lane, and res["refocus"] is its RefocusResult
     """
+    if refocus is not None and detect is None:
+        raise ValueError("refocus needs detect (the report list it refocuses)")
     ctx = ctx or default_context()
     on_device = isinstance(raw_rx1, DeviceArray) and isinstance(raw_rx2, DeviceArray)
     if on_device:                      # echoes synthesised on the GPU: the pulse shift is two views, nothing is uploaded
@@ -377,8 +381,14 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
         if detect is not None:                              # CFAR + refine on the planes of this call; the report list comes back
             from . import gmti
             slot = ctx.alloc(detect.slot_bytes())
+            refocused = None
             try:
                 gmti.enqueue(ctx, bufs["dpca_mag"].ptr, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, detect, cal_phase, slot.ptr)
+                if refocus is not None:                     # enqueued behind refine on this lane; an overflowed list raises here
+                    from .refocus import refocus_slot
+                    refocused = refocus_slot(ctx, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, refocus, ra, slot.ptr,
+                                             detect.max_detections, wavelength_m=center_wavelength_m,
+                                             platform_speed_mps=platform_speed_mps, prf_hz=prf_hz, cal_phase=cal_phase)
                 raw = gmti.fetch_slot(ctx, slot.ptr, detect.max_detections)
             finally:
                 slot.release()
@@ -388,6 +398,8 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
         res = {"range_axis": ra, "cross_range": ca, "max_mag": max_mag, "sum_interf": sum_interf, "fused_products": fused}
         if report is not None:
             res["detections"] = report
+        if refocus is not None:
+            res["refocus"] = refocused
         names = ["slc1"] + (["slc2"] if (return_slc2 or not fused) else []) + ["slc1_mag", "dpca_mag", "ati_phase_masked"] + \
                 (["ati_phase"] if "ati_phase" in bufs else [])
         if device_output:
