@@ -1,4 +1,4 @@
-// Internal launch interface between the C ABI (sarx_api.hip) and the kernels.
+// Internal launch interface between the C ABI (the api_*.hip host units) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

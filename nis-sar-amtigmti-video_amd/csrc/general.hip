@@ -9,7 +9,7 @@
 // a 32768-point line runs as 128 x 256 over the azimuth tile kernel and the 256-point line kernel,
 // its spectrum staying in the permuted order the inverse consumes.
 // This path is correctness-first: phases are separate element-wise launches and every transform
-// makes several HBM round trips.  The power-of-two path (sarx_api.hip) is the tuned one.
+// makes several HBM round trips.  The power-of-two path (api_csa.hip) is the tuned one.
 #include "general.h"
 
 #include <cmath>

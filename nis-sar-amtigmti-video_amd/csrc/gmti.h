@@ -1,4 +1,4 @@
-// Internal launch interface of the GMTI detector (gmti.hip) for the C ABI (sarx_api.hip, include/sarx_gmti.h).
+// Internal launch interface of the GMTI detector (gmti.hip) for the C ABI (api_gmti.hip, include/sarx_gmti.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,4 +1,4 @@
-// Internal launch interface of the GMTI refocus (refocus.hip) for the C ABI (sarx_api.hip, include/sarx_refocus.h).
+// Internal launch interface of the GMTI refocus (refocus.hip) for the C ABI (api_gmti.hip, include/sarx_refocus.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
