@@ -185,6 +185,39 @@ REFOCUS_SIGNATURES = {
     "sarx_refocus_dev": (_i, [_vp, _vp, _vp, _i, _i, _P(RefocusParams), _vp, _vp, _i, _vp, _vp, _vp]),
 }
 
+# include/sarx_balance.h: the two-channel balance, a fourth table bound the same way
+BALANCE_MIN_BLOCK, BALANCE_MAX_BLOCK, BALANCE_MAX_BLOCKS = 8, 4096, 65536     # SARX_BALANCE_MIN_BLOCK, _MAX_BLOCK, _MAX_BLOCKS
+BALANCE_LS, BALANCE_PHASE = 0, 1
+BALANCE_NEAREST, BALANCE_BILINEAR = 0, 1
+
+
+class BalanceParams(C.Structure):
+    """sarx_balance_params (40 bytes)"""
+    _fields_ = [("block_az", C.c_int32), ("block_rg", C.c_int32), ("mode", C.c_int32), ("interp", C.c_int32),
+                ("min_count", C.c_int32), ("reserved", C.c_int32), ("clip_power", C.c_double), ("min_coherence", C.c_double)]
+
+
+class BalanceHeader(C.Structure):
+    """sarx_balance_header: the first 64 bytes of a balance table"""
+    _fields_ = [("nb_az", C.c_uint32), ("nb_rg", C.c_uint32), ("n_valid", C.c_uint32), ("reserved", C.c_uint32),
+                ("w_re", C.c_double), ("w_im", C.c_double), ("coherence", C.c_double), ("s11", C.c_double), ("s22", C.c_double),
+                ("n", C.c_uint64)]
+
+
+class BalanceRecord(C.Structure):
+    """sarx_balance_record (64 bytes)"""
+    _fields_ = [("s12_re", C.c_double), ("s12_im", C.c_double), ("s11", C.c_double), ("s22", C.c_double), ("w_re", C.c_double),
+                ("w_im", C.c_double), ("coherence", C.c_float), ("n", C.c_uint32), ("valid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+BALANCE_SIGNATURES = {
+    "sarx_balance_check": (_i, [_P(BalanceParams), _i, _i]),
+    "sarx_balance_table_bytes": (_i, [_P(BalanceParams), _i, _i, _P(_sz)]),
+    "sarx_balance_workspace_bytes": (_i, [_P(BalanceParams), _i, _i, _P(_sz)]),
+    "sarx_balance_estimate_dev": (_i, [_vp, _vp, _vp, _i, _i, _P(BalanceParams), _vp, _vp]),
+    "sarx_balance_apply_dev": (_i, [_vp, _vp, _vp, _i, _i, _P(BalanceParams), _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -197,7 +230,8 @@ def load():
         raise SarxError(-3, f"{LIB_PATH} not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
                             "or `make -C nis-sar-amtigmti-video_amd/csrc` (hipcc, gfx950). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
+            list(BALANCE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -265,7 +265,7 @@ def two_channel_workspace(ctx, n_az, n_rg):
 def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp_rate_hzpsec, sample_rate_hz,
                    prf_hz, platform_speed_mps, range_ref_m, t_start_fast, mask_frac=0.05, cal_phase=0.0, *,
                    ctx=None, pulse_shift=True, return_slc2=True, unmasked_phase=False, device_output=False,
-                   workspace=None, fetch_stats=True, detect=None, refocus=None):
+                   workspace=None, fetch_stats=True, detect=None, refocus=None, balance=None):
     """The reference script's processing section in one call
     (sar_ati_dcpa_sim_csa.py:402-419,447-449): pulse shift, CSA focus of both
     channels, ATI/DPCA products, 5 % magnitude mask.  Nothing visits the host between the steps; with DeviceArray
@@ -293,9 +293,17 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
                           is downloaded
     refocus             : sarx.RefocusParams (needs detect): the GMTI refocus (sarx.gmti_refocus) runs on this call's device
                           images straight after the detector, on the same lane, and res["refocus"] is its RefocusResult
+    balance             : sarx.BalanceParams: channel 2's image is balanced in place against channel 1's (sarx.channel_balance)
+                          on this call's lane once both are focused; the products come from the separate ATI/DPCA launch on the
+                          balanced pair with cal_phase = 0 (the azimuth epilogue cannot form them: the weight needs channel 2's
+                          whole image), detect and refocus run on that pair with cal_phase = 0 too, the slc2 returned is the
+                          balanced one and res["balance"] is the block table (a ChannelBalance without images); its download
+                          waits for the lane.  cal_phase is not used
     """
     if refocus is not None and detect is None:
         raise ValueError("refocus needs detect (the report list it refocuses)")
+    if balance is not None:
+        balance.check()
     ctx = ctx or default_context()
     on_device = isinstance(raw_rx1, DeviceArray) and isinstance(raw_rx2, DeviceArray)
     if on_device:                      # echoes synthesised on the GPU: the pulse shift is two views, nothing is uploaded
@@ -307,6 +315,8 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
     if r1.shape != r2.shape:
         raise ValueError("the two channels must have the same shape")
     n_az, n_rg = r1.shape
+    if balance is not None:
+        balance.resolved(n_az, n_rg)                        # bad settings raise before anything is focused
     args = (center_wavelength_m, pulse_width_sec, chirp_rate_hzpsec, sample_rate_hz, prf_hz,
             platform_speed_mps, range_ref_m, t_start_fast)
     plan = _get_plan(ctx, n_az, n_rg, args, _ffi.FUSE_RANGE)
@@ -352,7 +362,7 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
                     early["slc1"] = bufs["slc1"].download_begin(np.complex64, (n_az, n_rg))
                 d_raw2.upload_unordered(r2)
             src2 = r2 if on_device else d_raw2
-            if have_max and not unmasked_phase:
+            if have_max and not unmasked_phase and balance is None:
                 try:                                        # channel 2: the products come out of its last azimuth launch
                     plan.set_ati(bufs["slc1"], bufs["d_max"], mask_frac, cal_phase, bufs["ati_phase_masked"], bufs["slc1_mag"],
                                  bufs["dpca_mag"], keep_image=return_slc2 or detect is not None)
@@ -367,6 +377,12 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
         finally:
             plan.set_ati(None)
             plan.set_max_slot(None)
+        balanced = None
+        if balance is not None:                             # slc2 <- w slc2 in place; everything below sees a balanced pair
+            from .balance import ChannelBalance, balance_dev
+            raw_table, clip = balance_dev(ctx, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, balance, bufs["slc2"].ptr)
+            balanced = ChannelBalance(raw_table, (n_az, n_rg), balance.block, balance.interp, clip)
+            cal_phase = 0.0
         if not fused:
             if unmasked_phase or not have_max:              # ATI launch, then the mask with the threshold taken on the device
                 bufs["ati_phase"] = ctx.alloc(n * 4)
@@ -400,6 +416,8 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
             res["detections"] = report
         if refocus is not None:
             res["refocus"] = refocused
+        if balanced is not None:
+            res["balance"] = balanced
         names = ["slc1"] + (["slc2"] if (return_slc2 or not fused) else []) + ["slc1_mag", "dpca_mag", "ati_phase_masked"] + \
                 (["ati_phase"] if "ati_phase" in bufs else [])
         if device_output:
