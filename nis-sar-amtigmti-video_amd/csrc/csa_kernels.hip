@@ -331,7 +331,8 @@ __global__ __launch_bounds__((AzCfg<R, W>::THREADS)) void az_tile_kernel(AzArgs 
             for (int r = 0; r < RLp; ++r)
                 s1v[b * RLp + r] = a.ati_s1[(out_base + (size_t)E::out_index(t, b, r) * a.out_m_stride) * a.n_rg + col];
     }
-    stockham_run<R, W, INV, false>(v, t, c, lds, a.tw_r);
+    // 128 rows = 16 x 8: the one tile size whose second stage needs powers up to w^7 - each evaluated directly (fft_core.hpp)
+    stockham_run<R, W, INV, false, 0, false, (R == 128)>(v, t, c, lds, a.tw_r);
     constexpr int RL = E::R_last;
     float vmax = 0.f;
 #pragma unroll

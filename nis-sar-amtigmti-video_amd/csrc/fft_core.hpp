@@ -238,7 +238,11 @@ template <int N, int D, bool INV> __device__ __forceinline__ cf stage_twiddle(in
 
 // One Stockham stage on registers.  v holds P points: butterfly b (j = t + b*T)
 // occupies v[b*R .. b*R+R-1].
-template <int N, int T, int R, int NS, bool INV>
+// DIRECT_TW: every w^r = exp(-+ 2 pi i r k / D) is evaluated on its own (r k < D: the argument is still exact) instead of being
+// multiplied up from w^1.  A product w^r carries r times the error of w^1: with the radix-8 second stage of the 128-point
+// transform that was 5e-7 of an element against 1.3e-7 for correctly rounded twiddles.  Twelve more quarter-rate instructions per
+// 16 points: for kernels that wait for memory (the azimuth tiles), not for the range kernels, which wait for the vector unit.
+template <int N, int T, int R, int NS, bool INV, bool DIRECT_TW = false>
 __device__ __forceinline__ void stage_compute(cf* v, int t, const cf* __restrict__ tw) {
     constexpr int P = N / T;
     constexpr int B = P / R;
@@ -246,7 +250,12 @@ __device__ __forceinline__ void stage_compute(cf* v, int t, const cf* __restrict
     for (int b = 0; b < B; ++b) {
         if constexpr (NS > 1) {
             const int j = t + b * T;
-            apply_twiddle_powers<R>(v + b * R, stage_twiddle<N, NS * R, INV>(j % NS, tw));
+            if constexpr (DIRECT_TW) {
+#pragma unroll
+                for (int r = 1; r < R; ++r) v[b * R + r] = cmul(v[b * R + r], stage_twiddle<N, NS * R, INV>(r * (j % NS), tw));
+            } else {
+                apply_twiddle_powers<R>(v + b * R, stage_twiddle<N, NS * R, INV>(j % NS, tw));
+            }
         }
         dft<R, INV>(v + b * R);
     }
@@ -294,20 +303,20 @@ template <bool WAVE_LOCAL> __device__ __forceinline__ void exchange_sync() {
         __syncthreads();
     }
 }
-template <int N, int W, bool INV, bool REV, int S = 0, bool WAVE_LOCAL = false>
+template <int N, int W, bool INV, bool REV, int S = 0, bool WAVE_LOCAL = false, bool DIRECT_TW = false>
 __device__ __forceinline__ void stockham_run(cf* v, int t, int c, cf* lds, const cf* __restrict__ tw) {
     using PL = Plan<N>;
     static_assert(!WAVE_LOCAL || PL::T == 64, "wave-local transforms span exactly one wavefront");
     constexpr int R = PL::template radix<REV>(S);
     constexpr int NS = PL::template ns_before<REV>(S);
-    stage_compute<N, PL::T, R, NS, INV>(v, t, tw);
+    stage_compute<N, PL::T, R, NS, INV, DIRECT_TW>(v, t, tw);
     if constexpr (S + 1 < PL::nstages) {
         constexpr int R2 = PL::template radix<REV>(S + 1);
         if constexpr (S > 0) exchange_sync<WAVE_LOCAL>();   // previous gather done before overwrite
         stage_scatter<N, PL::T, R, NS, W>(v, t, c, lds);
         exchange_sync<WAVE_LOCAL>();
         stage_gather<N, PL::T, R2, W>(v, t, c, lds);
-        stockham_run<N, W, INV, REV, S + 1, WAVE_LOCAL>(v, t, c, lds, tw);
+        stockham_run<N, W, INV, REV, S + 1, WAVE_LOCAL, DIRECT_TW>(v, t, c, lds, tw);
     }
 }
 

@@ -1,6 +1,10 @@
 """The wave-private azimuth tiles (az_wave.hip, SARX_AZ_IMPL=1, the default) against az_tile_kernel (SARX_AZ_IMPL=0) at
 16384^2 on the same device input: each of the four 128-point steps of the four-step transform (sarx_csa_pass ids 110-113)
-and a whole focus.  The transforms add in another order, so the images agree to rounding, not bit for bit."""
+and a whole focus.  The transforms add in another order, so the images agree to rounding, not bit for bit.
+
+Role: the full-size cross-check of the two routes (two workgroups and more per tile row, 2 GiB images, the whole focus).  Neither
+side is a reference here; what each launch must produce is stated by tests/test_gpu_az_steps.py, which holds both routes - and every
+other four-step size, width and epilogue - by the complex128 step oracle on images a few columns wide, in seconds."""
 import numpy as np
 import pytest
 
