@@ -218,6 +218,43 @@ BALANCE_SIGNATURES = {
     "sarx_balance_apply_dev": (_i, [_vp, _vp, _vp, _i, _i, _P(BalanceParams), _vp, _vp, _vp]),
 }
 
+# include/sarx_track.h: the GMTI tracker, a fifth table bound the same way
+TRACK_MAX_TRACKS, TRACK_MAX_DETECTIONS = 16384, 65536                         # SARX_TRACK_MAX_TRACKS, _MAX_DETECTIONS
+TRACK_FREE, TRACK_TENTATIVE, TRACK_CONFIRMED = 0, 1, 2
+TRACK_OK, TRACK_ERR_SLOT_OVERFLOW, TRACK_ERR_TABLE_OVERFLOW = 0, 1, 2
+
+
+class TrackParams(C.Structure):
+    """sarx_track_params (64 bytes)"""
+    _fields_ = [("gate_az", C.c_double), ("gate_rg", C.c_double), ("alpha", C.c_double), ("beta", C.c_double),
+                ("birth_ratio", C.c_double), ("confirm_hits", C.c_int32), ("confirm_window", C.c_int32), ("max_misses", C.c_int32),
+                ("max_tracks", C.c_int32), ("max_detections", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TrackHeader(C.Structure):
+    """sarx_track_header: the first 64 bytes of a track table"""
+    _fields_ = [("n_live", C.c_uint32), ("n_confirmed", C.c_uint32), ("next_id", C.c_int32), ("frames_done", C.c_uint32),
+                ("births_total", C.c_uint32), ("drops_total", C.c_uint32), ("error", C.c_uint32), ("error_frame", C.c_int32),
+                ("max_tracks", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class TrackSlot(C.Structure):
+    """sarx_track_slot (96 bytes)"""
+    _fields_ = [("p_i", C.c_double), ("p_j", C.c_double), ("v_i", C.c_double), ("v_j", C.c_double), ("sum_re", C.c_double),
+                ("sum_im", C.c_double), ("sum_power", C.c_double), ("max_ratio", C.c_double), ("id", C.c_int32),
+                ("status", C.c_uint32), ("hits", C.c_uint32), ("misses", C.c_uint32), ("age", C.c_uint32), ("hist", C.c_uint32),
+                ("last_frame", C.c_int32), ("last_report", C.c_int32)]
+
+
+TRACK_SIGNATURES = {
+    "sarx_track_check": (_i, [_P(TrackParams)]),
+    "sarx_track_table_bytes": (_i, [_P(TrackParams), _P(_sz)]),
+    "sarx_track_workspace_bytes": (_i, [_P(TrackParams), _P(_sz)]),
+    "sarx_track_init_dev": (_i, [_vp, _P(TrackParams), _vp]),
+    "sarx_track_step_dev": (_i, [_vp, _P(TrackParams), _vp, _i, _vp, _vp, _vp]),
+    "sarx_track_run_dev": (_i, [_vp, _P(TrackParams), _vp, _sz, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -231,7 +268,7 @@ def load():
                             "or `make -C nis-sar-amtigmti-video_amd/csrc` (hipcc, gfx950). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
-            list(BALANCE_SIGNATURES.items()):
+            list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

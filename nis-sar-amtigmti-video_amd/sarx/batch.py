@@ -210,7 +210,8 @@ class TwoChannelBatch:
     stack="detections": the GMTI report list of the frame (sarx.gmti: CFAR on the DPCA plane, refined with both images), a
     fixed-size block of header (count, overflow flag) + `detect.max_detections` reports written by the detector straight at
     the frame's place in the stack buffer (196 KiB per frame at the default 4096 reports, whatever the frame size);
-    b.detections(f) decodes it.
+    b.detections(f) decodes it.  With track=TrackParams(...) the GMTI tracker (sarx.track) then runs over the assembled stack in
+    frame order, enqueued behind the last gather; b.tracks() decodes its table.  Without track= nothing of it exists.
 
     The stack lives in one device buffer [rounds][world][slot]; a frame's slot is produced directly at its place
     and each round is gathered IN PLACE (send = recv + rank * slot), so there is no send buffer to recycle and no
@@ -222,11 +223,14 @@ class TwoChannelBatch:
 
     def __init__(self, ctx, n, n_frames, world=1, rank=0, stack="multilook", looks=16, rccl=False, host_comm=None,
                  seed_base=1000, flags=None, mask_frac=0.05, resident=True, fused_mask=True, fused_ati=True, scene="noise",
-                 scene_scale=1.0, lanes=None, detect=None, refocus=None):
+                 scene_scale=1.0, lanes=None, detect=None, refocus=None, track=None,
+                 frame_dt_s=0.1):
         from . import _ffi, radar
         from .engine import CsaPlan
         if stack not in STACKS:
             raise ValueError(f"stack must be one of {STACKS}")
+        if track is not None and stack != "detections":
+            raise ValueError('track needs stack="detections"')
         if world > 1 and not rccl and host_comm is None:
             raise ValueError("world > 1 needs a transport (rccl=True or host_comm)")
         self.ctx, self.n, self.n_frames, self.world, self.rank = ctx, int(n), int(n_frames), int(world), int(rank)
@@ -272,6 +276,7 @@ class TwoChannelBatch:
         self.refocus_params = None
         if refocus is not None and stack != "detections":
             raise ValueError('refocus needs stack="detections"')
+        self.track_params, self.frame_dt_s = None, float(frame_dt_s)     # c3_scene advances its movers by frame * 0.1 s
         if stack == "detections":
             from .gmti import GmtiParams
             self.detect = detect if detect is not None else GmtiParams()
@@ -292,6 +297,13 @@ class TwoChannelBatch:
         self.n_rounds = rounds(self.n_frames, self.world)
         self.mine = shard_frames(self.n_frames, self.world, self.rank)
         self.d_stack = ctx.alloc(self.slot_bytes * self.world * self.n_rounds)
+        if track is not None:                                        # the table, the assoc rows and the workspace: made once, here
+            import dataclasses
+            from . import track as trk
+            self.track_params = dataclasses.replace(track, max_detections=self.detect.max_detections)
+            self._track_cp = self.track_params.c_params()
+            self.d_track = (ctx.alloc(trk.table_bytes(self._track_cp)), ctx.alloc(trk.workspace_bytes(self._track_cp)),
+                            ctx.alloc(self.n_frames * self.detect.max_detections * 4))
         # echoes: resident = every frame of this rank has its own two channel buffers, synthesised once by prepare()
         # (BASELINE config 5: inputs in HBM before the clock starts; 1 GiB per 8192^2 two-channel frame, 64 GiB for the
         # whole batch on one GPU of 288 GB); otherwise one pair of buffers refilled inside run() frame by frame
@@ -463,8 +475,37 @@ class TwoChannelBatch:
                 ctx.set_range_cus(0)
         if self.lanes > 1:
             ctx.lanes_join()                                        # whatever follows on any lane sees every frame finished
+        if self.track_params is not None:
+            self._track()
         if self.rccl and self.world > 1:
             ctx.comm_sync()
+
+    def _track(self):
+        """The tracker over the assembled stack, frame f at slot f, on lane 0: behind every frame (lanes_join) and, with RCCL, behind
+        every gather on the device (comm_fence_compute).  Only enqueues; the stride skips the refocus records."""
+        from . import track as trk
+        if self.rccl and self.world > 1:
+            self.ctx.comm_fence_compute()
+        table, ws, assoc = self.d_track
+        trk.enqueue_init(self.ctx, self._track_cp, table.ptr)
+        trk.enqueue_run(self.ctx, self._track_cp, self.d_stack.ptr, self.slot_bytes, self.n_frames, table.ptr, assoc.ptr, ws.ptr)
+
+    def tracks(self):
+        """stack="detections" with track=: the TrackResult of the run (raises TrackOverflowError if the tracker stopped).  Range
+        rate from the focus's range spacing and frame_dt_s, ATI speed with the lag of detections()."""
+        from . import track as trk
+        if self.track_params is None:
+            raise ValueError("tracks() needs track=")
+        table, _, d_assoc = self.d_track
+        md = self.detect.max_detections
+        raw = table.download(np.uint8, (table.nbytes,))
+        assoc = d_assoc.download(np.int32, (self.n_frames, md))
+        stack = self.stack().reshape(self.n_frames, -1).view(np.uint8)
+        ra = self._lane_state[0]["plan"].axes()[0]
+        lam, prf = self.focus_args[0], self.focus_args[4]
+        lag = self.detect.lag_s if self.detect.lag_s is not None else 1.0 / prf
+        dr = float(ra[-1] - ra[0]) / (len(ra) - 1)
+        return trk.TrackResult(raw, assoc, [trk._slot_ij(stack[f], md) for f in range(self.n_frames)], self.frame_dt_s, dr, lam / (4.0 * lag))
 
     def _run_rounds(self):
         from ._ffi import check
@@ -531,3 +572,6 @@ class TwoChannelBatch:
             st["plan"].close()
         if hasattr(self, "d_gmax"):
             self.d_gmax.release()
+        if self.track_params is not None:
+            for b in self.d_track:
+                b.release()
