@@ -13,6 +13,7 @@ from .tdbp import (tdbp_gpu, run_physics_spotlight, calculate_raw_snr_db, genera
 from .gmti import GmtiOverflowError, GmtiParams, GmtiReport, gmti_detect
 from .refocus import RefocusParams, RefocusResult, gmti_refocus
 from .balance import BalanceParams, ChannelBalance, channel_balance
+from .coherence import CoherenceParams, CoherenceResult, coherence, coherence_stack
 from .track import GmtiTracker, TrackOverflowError, TrackParams, TrackResult, gmti_track
 from .focus import (FocusFuture, ati_dpca, clear_plan_cache, dpca_pulse_shift, focus_ati_dpca, focus_stream, phase_balance,
                     sar_focus_csa, sar_focus_csa_async, two_channel_workspace)
@@ -22,4 +23,5 @@ __all__ = ["SarxError", "Context", "CsaPlan", "FocusLanes", "add_noise_rel_dev",
            "run_bistatic_physics_gpu", "run_moving_physics", "run_custom_physics", "sar_focus_rda", "calculate_snr_db", "add_ocean_noise", "add_noise_dev", "power_stats", "tdbp_gpu", "run_physics_spotlight", "calculate_raw_snr_db",
            "generate_noise_tensor", "batch_constants", "orbit_arc", "TdbpPlan", "gmti_detect", "GmtiParams", "GmtiReport",
            "GmtiOverflowError", "gmti_refocus", "RefocusParams", "RefocusResult", "channel_balance", "BalanceParams", "ChannelBalance",
+           "coherence", "coherence_stack", "CoherenceParams", "CoherenceResult",
            "gmti_track", "GmtiTracker", "TrackParams", "TrackResult", "TrackOverflowError"]

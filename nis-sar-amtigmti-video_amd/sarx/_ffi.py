@@ -255,6 +255,29 @@ TRACK_SIGNATURES = {
     "sarx_track_run_dev": (_i, [_vp, _P(TrackParams), _vp, _sz, _i, _vp, _vp, _vp]),
 }
 
+# include/sarx_coherence.h: the sliding-window coherence, a sixth table bound the same way
+COH_MAX_HALF = 16               # SARX_COH_MAX_HALF
+
+
+class CoherenceParams(C.Structure):
+    """sarx_coherence_params (32 bytes)"""
+    _fields_ = [("ha", C.c_int32), ("hr", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_double),
+                ("power_floor", C.c_double)]
+
+
+class CoherenceSummary(C.Structure):
+    """sarx_coherence_summary (64 bytes)"""
+    _fields_ = [("n_tested", C.c_uint64), ("n_changed", C.c_uint64), ("sum_coh", C.c_double), ("n_az", C.c_uint32),
+                ("n_rg", C.c_uint32), ("reserved", C.c_uint32 * 8)]
+
+
+COHERENCE_SIGNATURES = {
+    "sarx_coherence_check": (_i, [_P(CoherenceParams), _i, _i]),
+    "sarx_coherence_workspace_bytes": (_i, [_P(CoherenceParams), _i, _i, _P(_sz)]),
+    "sarx_coherence_pair_dev": (_i, [_vp, _vp, _vp, _i, _i, _P(CoherenceParams), _vp, _vp, _vp, _vp, _vp]),
+    "sarx_coherence_stack_dev": (_i, [_vp, _vp, _i, _sz, _i, _i, _i, _P(CoherenceParams), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -268,7 +291,7 @@ def load():
                             "or `make -C nis-sar-amtigmti-video_amd/csrc` (hipcc, gfx950). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
-            list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()):
+            list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -265,7 +265,7 @@ def two_channel_workspace(ctx, n_az, n_rg):
 def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp_rate_hzpsec, sample_rate_hz,
                    prf_hz, platform_speed_mps, range_ref_m, t_start_fast, mask_frac=0.05, cal_phase=0.0, *,
                    ctx=None, pulse_shift=True, return_slc2=True, unmasked_phase=False, device_output=False,
-                   workspace=None, fetch_stats=True, detect=None, refocus=None, balance=None):
+                   workspace=None, fetch_stats=True, detect=None, refocus=None, balance=None, coherence=None):
     """The reference script's processing section in one call
     (sar_ati_dcpa_sim_csa.py:402-419,447-449): pulse shift, CSA focus of both
     channels, ATI/DPCA products, 5 % magnitude mask.  Nothing visits the host between the steps; with DeviceArray
@@ -299,11 +299,19 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
                           whole image), detect and refocus run on that pair with cal_phase = 0 too, the slc2 returned is the
                           balanced one and res["balance"] is the block table (a ChannelBalance without images); its download
                           waits for the lane.  cal_phase is not used
+    coherence           : sarx.CoherenceParams: the sliding-window coherence (sarx.coherence) of the two images the products were
+                          formed from (after the balance, if one is asked for) runs on this call's lane and res["coherence"] is
+                          its fp32 map; with a threshold also res["coherence_mask"] (uint8: 0 not tested, 1 unchanged, 2 changed)
+                          and res["coherence_n_tested"], ["coherence_n_changed"], ["coherence_mean"] (the three figures are
+                          fetched unless device_output is set with fetch_stats=False).  Channel 2's image is kept on the device
+                          for it even with return_slc2=False, but not returned
     """
     if refocus is not None and detect is None:
         raise ValueError("refocus needs detect (the report list it refocuses)")
     if balance is not None:
         balance.check()
+    if coherence is not None:
+        coherence.check()
     ctx = ctx or default_context()
     on_device = isinstance(raw_rx1, DeviceArray) and isinstance(raw_rx2, DeviceArray)
     if on_device:                      # echoes synthesised on the GPU: the pulse shift is two views, nothing is uploaded
@@ -365,7 +373,7 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
             if have_max and not unmasked_phase and balance is None:
                 try:                                        # channel 2: the products come out of its last azimuth launch
                     plan.set_ati(bufs["slc1"], bufs["d_max"], mask_frac, cal_phase, bufs["ati_phase_masked"], bufs["slc1_mag"],
-                                 bufs["dpca_mag"], keep_image=return_slc2 or detect is not None)
+                                 bufs["dpca_mag"], keep_image=return_slc2 or detect is not None or coherence is not None)
                     fused = True
                 except _ffi.SarxError:
                     fused = False
@@ -410,6 +418,18 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
                 slot.release()
             report = gmti.decode_slot(raw, detect, ra, ca, center_wavelength_m, platform_speed_mps,
                                       detect.lag_s if detect.lag_s is not None else 1.0 / prf_hz)
+        coh_summary = None
+        if coherence is not None:                           # on the pair the products came from
+            from .coherence import SUMMARY_BYTES, SUMMARY_DTYPE, CoherenceResult, coherence_dev
+            rule = coherence.threshold is not None
+            fetch = rule and (fetch_stats or not device_output)
+            planes = coherence_dev(ctx, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, coherence, mask=rule, summary=fetch)
+            bufs.update({"coherence": planes["coh"], "coherence_summary": planes["summary"], "coherence_workspace": planes["workspace"]})
+            if rule:
+                bufs["coherence_mask"] = planes["mask"]
+            bufs = {k: v for k, v in bufs.items() if v is not None}
+            if fetch:
+                coh_summary = CoherenceResult(summary=bufs["coherence_summary"].download(np.uint8, (SUMMARY_BYTES,)).copy().view(SUMMARY_DTYPE)[0])
         max_mag, sum_interf = ctx.ati_stats() if (fetch_stats or not device_output) else (None, None)   # the only host synchronisation of the chain
         res = {"range_axis": ra, "cross_range": ca, "max_mag": max_mag, "sum_interf": sum_interf, "fused_products": fused}
         if report is not None:
@@ -419,7 +439,10 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
         if balanced is not None:
             res["balance"] = balanced
         names = ["slc1"] + (["slc2"] if (return_slc2 or not fused) else []) + ["slc1_mag", "dpca_mag", "ati_phase_masked"] + \
-                (["ati_phase"] if "ati_phase" in bufs else [])
+                (["ati_phase"] if "ati_phase" in bufs else []) + [k for k in ("coherence", "coherence_mask") if k in bufs]
+        if coh_summary is not None:
+            res.update({"coherence_n_tested": coh_summary.n_tested, "coherence_n_changed": coh_summary.n_changed,
+                        "coherence_mean": coh_summary.mean_coh})
         if device_output:
             for k in names:
                 res[k] = bufs[k]
@@ -427,7 +450,8 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
         else:                                               # every plane's download in flight at once, then collected in order
             for k in names:
                 if k not in early:
-                    early[k] = bufs[k].download_begin(np.complex64 if k in ("slc1", "slc2") else np.float32, (n_az, n_rg))
+                    early[k] = bufs[k].download_begin(np.complex64 if k in ("slc1", "slc2") else np.uint8 if k == "coherence_mask" else np.float32,
+                                                       (n_az, n_rg))
             for k in names:
                 res[k] = early.pop(k).result().T
         return res
