@@ -278,6 +278,17 @@ COHERENCE_SIGNATURES = {
     "sarx_coherence_stack_dev": (_i, [_vp, _vp, _i, _sz, _i, _i, _i, _P(CoherenceParams), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
 }
 
+# include/sarx_oscfar.h: the ordered-statistic CFAR launch, a seventh table bound the same way
+class OscfarParams(C.Structure):
+    """sarx_oscfar_params (40 bytes)"""
+    _fields_ = [("base", GmtiParams), ("rank", C.c_int32), ("flags", C.c_int32)]
+
+
+OSCFAR_SIGNATURES = {
+    "sarx_oscfar_check": (_i, [_P(OscfarParams)]),
+    "sarx_gmti_oscfar_dev": (_i, [_vp, _vp, _i, _i, _P(OscfarParams), _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -291,7 +302,7 @@ def load():
                             "or `make -C nis-sar-amtigmti-video_amd/csrc` (hipcc, gfx950). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
-            list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()):
+            list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

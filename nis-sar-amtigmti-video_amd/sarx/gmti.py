@@ -7,6 +7,11 @@ Semantics (the kernels implement them; the host only derives the fields from the
   N = |T|; a cell is tested when N >= N_full / 2 and detected when P > alpha * mean_T(P), alpha = N_full (pfa^(-1/N_full) - 1) -
   edge cells with a smaller N keep that full-window alpha.  A detected cell is reported when its P is the maximum over its guard
   box (ties: the smaller linear index).  Reports come sorted by (i, j); more than max_detections of them raise.
+
+method="os" (include/sarx_oscfar.h, csrc/oscfar.hip) replaces the mean by an ordered statistic: with k = ceil(rank N / N_full) a
+cell is detected when P > 0 and at least k of its training cells have alpha * P_t < P, i.e. when P > alpha * x_(k) for the k-th
+smallest training power x_(k).  alpha = os_cfar_alpha(pfa, N_full, rank); edge cells keep that full-window alpha, as in CA.  The
+report's `mean` is then x_(k), the level the cell was held against.  Everything else - peak rule, slot, refine - is shared.
 """
 from __future__ import annotations
 
@@ -50,16 +55,64 @@ def cfar_alpha(pfa, n):
     return n * (pfa ** (-1.0 / n) - 1.0)
 
 
+def _os_log_pfa(alpha, n, rank):
+    return -math.fsum(math.log1p(alpha / (n - i)) for i in range(rank))
+
+
+def os_cfar_pfa(alpha, n, rank):
+    """False-alarm rate of OS-CFAR on exponentially distributed power: prod_{i < rank} (n - i) / (n - i + alpha), in logs."""
+    return math.exp(_os_log_pfa(alpha, n, rank))
+
+
+def os_cfar_alpha(pfa, n, rank):
+    """OS-CFAR threshold factor for exponentially distributed power: the alpha at which os_cfar_pfa(alpha, n, rank) = pfa, by
+    bisection (the rate falls monotonically with alpha).  n = rank = 1 gives 1 / pfa - 1."""
+    if not (0.0 < pfa < 1.0) or n < 1 or not 1 <= rank <= n:
+        raise ValueError("pfa must lie in (0, 1) and the rank in 1 .. n")
+    want = math.log(pfa)
+    lo, hi = 0.0, 1.0
+    while _os_log_pfa(hi, n, rank) > want:
+        lo, hi = hi, 2.0 * hi
+    while True:
+        mid = 0.5 * (lo + hi)
+        if not lo < mid < hi:
+            return hi
+        if _os_log_pfa(mid, n, rank) > want:
+            lo = mid
+        else:
+            hi = mid
+
+
+METHODS = ("ca", "os")
+
+
 @dataclass
 class GmtiParams:
-    """Detector settings: half-widths (azimuth, range), false-alarm rate or alpha, capacity of the report list, and the lag
-    between the co-registered channels (None = one pulse, 1 / prf)."""
+    """Detector settings: half-widths (azimuth, range), false-alarm rate or alpha, capacity of the report list, the lag
+    between the co-registered channels (None = one pulse, 1 / prf), the method ("ca" cell averaging, "os" ordered statistic) and
+    the ordered statistic's rank (None = (3 N_full) // 4)."""
     guard: Tuple[int, int] = (2, 2)
     train: Tuple[int, int] = (8, 8)
     pfa: float = 1e-6
     alpha: Optional[float] = None
     max_detections: int = 4096
     lag_s: Optional[float] = None
+    method: str = "ca"
+    os_rank: Optional[int] = None
+
+    def rank(self):
+        """The ordered statistic's rank for method="os" (None for "ca")."""
+        if self.method not in METHODS:
+            raise ValueError(f"method {self.method!r}: one of {METHODS}")
+        if self.method == "ca":
+            if self.os_rank is not None:
+                raise ValueError('os_rank needs method="os"')
+            return None
+        nf = n_full(tuple(int(x) for x in self.guard), tuple(int(x) for x in self.train))
+        rank = (3 * nf) // 4 if self.os_rank is None else int(self.os_rank)
+        if not 1 <= rank <= nf:
+            raise ValueError(f"os_rank {rank} must be 1 .. N_full = {nf}")
+        return rank
 
     def resolved(self):
         ga, gr = (int(x) for x in self.guard)
@@ -71,20 +124,29 @@ class GmtiParams:
         nf = n_full((ga, gr), (ta, tr))
         if nf < 1:
             raise ValueError("the training set is empty")
-        alpha = float(self.alpha) if self.alpha is not None else cfar_alpha(float(self.pfa), nf)
+        rank = self.rank()
+        if self.alpha is not None:
+            alpha = float(self.alpha)
+        else:
+            alpha = cfar_alpha(float(self.pfa), nf) if rank is None else os_cfar_alpha(float(self.pfa), nf, rank)
         if not (alpha > 0.0 and math.isfinite(alpha)):
             raise ValueError("alpha must be finite and > 0")
         if int(self.max_detections) < 1:
             raise ValueError("max_detections must be >= 1")
         return ga, gr, ta, tr, nf, alpha
 
-    def c_params(self):
+    def _base_params(self):
         ga, gr, ta, tr, nf, alpha = self.resolved()
         return _ffi.GmtiParams(ga, gr, ta, tr, alpha, (nf + 1) // 2, int(self.max_detections))
 
+    def c_params(self):
+        """sarx_gmti_params for method="ca", sarx_oscfar_params for method="os"."""
+        base = self._base_params()
+        return base if self.method == "ca" else _ffi.OscfarParams(base, self.rank(), 0)
+
     def slot_bytes(self):
         """Bytes of one device slot: header + max_detections reports (sarx_gmti_slot_bytes)."""
-        cp = self.c_params()
+        cp = self._base_params()
         n = C.c_size_t()
         lib = _ffi.load()
         check(lib.sarx_gmti_slot_bytes(C.byref(cp), C.byref(n)))
@@ -93,14 +155,17 @@ class GmtiParams:
 
 class GmtiReport:
     """Result of a detection: `detections` (structured array, DETECTION_DTYPE, sorted by (i, j)), `n_found`, the `alpha` used, the
-    unambiguous radial speed `v_ambiguity_mps` = lambda / (4 lag)."""
+    unambiguous radial speed `v_ambiguity_mps` = lambda / (4 lag), the `method` ("ca" / "os") and, for "os", the `rank` (else
+    None).  With "os" the `mean` field is the ordered statistic x_(rank), so `snr_db` is power over that level."""
 
-    def __init__(self, detections, alpha, v_ambiguity_mps, n_full_cells):
+    def __init__(self, detections, alpha, v_ambiguity_mps, n_full_cells, method="ca", rank=None):
         self.detections = detections
         self.n_found = int(len(detections))
         self.alpha = float(alpha)
         self.v_ambiguity_mps = float(v_ambiguity_mps)
         self.n_full = int(n_full_cells)
+        self.method = method
+        self.rank = None if rank is None else int(rank)
 
     def __len__(self):
         return self.n_found
@@ -118,9 +183,10 @@ def enqueue(ctx, d_mag, d_slc1, d_slc2, n_az, n_rg, params, cal_phase, slot_ptr)
     """CFAR + refine launches on the ctx's current lane into the slot at slot_ptr (header, then the report list).  Device
     pointers, [n_az x n_rg] row-major; only enqueues."""
     cp = params.c_params()
-    check(ctx.lib.sarx_gmti_cfar_dev(ctx.h, d_mag, int(n_az), int(n_rg), C.byref(cp), slot_ptr + HEADER_BYTES, slot_ptr), ctx.h)
+    launch = ctx.lib.sarx_gmti_cfar_dev if params.method == "ca" else ctx.lib.sarx_gmti_oscfar_dev
+    check(launch(ctx.h, d_mag, int(n_az), int(n_rg), C.byref(cp), slot_ptr + HEADER_BYTES, slot_ptr), ctx.h)
     check(ctx.lib.sarx_gmti_refine_dev(ctx.h, d_slc1, d_slc2, int(n_az), int(n_rg), float(cal_phase), slot_ptr + HEADER_BYTES,
-                                       slot_ptr, cp.max_detections), ctx.h)
+                                       slot_ptr, int(params.max_detections)), ctx.h)
 
 
 def fetch_slot(ctx, slot_ptr, max_detections):
@@ -159,7 +225,7 @@ def decode_slot(raw, params, range_axis, cross_range, wavelength_m, platform_spe
     # further away for slc1, so angle(slc1 conj(slc2)) = -4 pi v_los lag / lambda; it is imaged R v_los / V earlier in azimuth
     out["v_los_mps"] = -lam * out["ati_phase"] / (4.0 * math.pi * lag)
     out["cross_range_relocated_m"] = out["cross_range_m"] + out["range_m"] * out["v_los_mps"] / float(platform_speed_mps)
-    return GmtiReport(out, alpha, lam / (4.0 * lag), nf)
+    return GmtiReport(out, alpha, lam / (4.0 * lag), nf, params.method, params.rank())
 
 
 def _plane_ptr(ctx, x, n_az, n_rg, dtype, temps):
@@ -185,7 +251,7 @@ def _plane_ptr(ctx, x, n_az, n_rg, dtype, temps):
 
 
 def gmti_detect(slc1, slc2, range_axis, cross_range, *, wavelength_m, platform_speed_mps, lag_s, guard=(2, 2), train=(8, 8),
-                pfa=1e-6, alpha=None, cal_phase=0.0, max_detections=4096, dpca_mag=None, ctx=None):
+                pfa=1e-6, alpha=None, cal_phase=0.0, max_detections=4096, dpca_mag=None, ctx=None, method="ca", os_rank=None):
     """Detect movers in a focused two-channel pair and measure their radial speed.
 
     slc1, slc2  : [N_rg x N_az] complex host arrays (sar_focus_csa's views), or device images ([N_az x N_rg] DeviceArray /
@@ -193,9 +259,10 @@ def gmti_detect(slc1, slc2, range_axis, cross_range, *, wavelength_m, platform_s
     range_axis, cross_range : the focuser's axes (N_rg, N_az)
     lag_s       : time between the co-registered channels (1 / prf for the DPCA pulse shift)
     dpca_mag    : the DPCA magnitude plane (same layouts, fp32); None = computed here by the ATI/DPCA launch with cal_phase
+    method      : "ca" (cell averaging) or "os" (ordered statistic of rank os_rank, None = (3 N_full) // 4)
     Returns a GmtiReport; raises GmtiOverflowError if more than max_detections cells qualify."""
     from .engine import default_context
-    params = GmtiParams(tuple(guard), tuple(train), pfa, alpha, int(max_detections), lag_s)
+    params = GmtiParams(tuple(guard), tuple(train), pfa, alpha, int(max_detections), lag_s, method, os_rank)
     params.resolved()
     ctx = ctx or getattr(slc1, "ctx", None) or default_context()
     n_rg, n_az = len(range_axis), len(cross_range)
