@@ -289,6 +289,29 @@ OSCFAR_SIGNATURES = {
     "sarx_gmti_oscfar_dev": (_i, [_vp, _vp, _i, _i, _P(OscfarParams), _vp, _vp]),
 }
 
+# include/sarx_cluster.h: the GMTI plot extraction, an eighth table bound the same way
+CLUSTER_MAX_LINK, CLUSTER_MAX_DETECTIONS = 64, 16384                          # SARX_CLUSTER_MAX_LINK, _MAX_DETECTIONS
+
+
+class ClusterParams(C.Structure):
+    """sarx_cluster_params (16 bytes)"""
+    _fields_ = [("link_az", C.c_int32), ("link_rg", C.c_int32), ("min_members", C.c_int32), ("max_detections", C.c_int32)]
+
+
+class ClusterPlot(C.Structure):
+    """sarx_cluster_plot (64 bytes)"""
+    _fields_ = [("n_members", C.c_int32), ("peak_report", C.c_int32), ("i_min", C.c_int32), ("i_max", C.c_int32), ("j_min", C.c_int32),
+                ("j_max", C.c_int32), ("sum_power", C.c_double), ("centroid_i", C.c_double), ("centroid_j", C.c_double),
+                ("max_ratio", C.c_double), ("reserved", C.c_uint32 * 2)]
+
+
+CLUSTER_SIGNATURES = {
+    "sarx_cluster_check": (_i, [_P(ClusterParams)]),
+    "sarx_cluster_plots_bytes": (_i, [_P(ClusterParams), _P(_sz)]),
+    "sarx_cluster_step_dev": (_i, [_vp, _P(ClusterParams), _vp, _vp, _vp, _vp]),
+    "sarx_cluster_run_dev": (_i, [_vp, _P(ClusterParams), _vp, _sz, _vp, _sz, _i, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -302,7 +325,8 @@ def load():
                             "or `make -C nis-sar-amtigmti-video_amd/csrc` (hipcc, gfx950). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
-            list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()):
+            list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()) + \
+            list(CLUSTER_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -212,6 +212,9 @@ class TwoChannelBatch:
     the frame's place in the stack buffer (196 KiB per frame at the default 4096 reports, whatever the frame size);
     b.detections(f) decodes it.  With track=TrackParams(...) the GMTI tracker (sarx.track) then runs over the assembled stack in
     frame order, enqueued behind the last gather; b.tracks() decodes its table.  Without track= nothing of it exists.
+    With cluster=ClusterParams(...) the detector writes into a scratch slot of the lane and the plot extraction (sarx.cluster) writes
+    the PLOT list at the frame's place in the stack, in the same layout: refocus and tracker then work on plots, b.detections(f)
+    decodes the plot list, and the plot records ride behind the refocus records (b.plots(f)).  Without cluster= nothing of it exists.
 
     The stack lives in one device buffer [rounds][world][slot]; a frame's slot is produced directly at its place
     and each round is gathered IN PLACE (send = recv + rank * slot), so there is no send buffer to recycle and no
@@ -224,13 +227,15 @@ class TwoChannelBatch:
     def __init__(self, ctx, n, n_frames, world=1, rank=0, stack="multilook", looks=16, rccl=False, host_comm=None,
                  seed_base=1000, flags=None, mask_frac=0.05, resident=True, fused_mask=True, fused_ati=True, scene="noise",
                  scene_scale=1.0, lanes=None, detect=None, refocus=None, track=None,
-                 frame_dt_s=0.1):
+                 frame_dt_s=0.1, cluster=None):
         from . import _ffi, radar
         from .engine import CsaPlan
         if stack not in STACKS:
             raise ValueError(f"stack must be one of {STACKS}")
         if track is not None and stack != "detections":
             raise ValueError('track needs stack="detections"')
+        if cluster is not None and stack != "detections":
+            raise ValueError('cluster needs stack="detections"')
         if world > 1 and not rccl and host_comm is None:
             raise ValueError("world > 1 needs a transport (rccl=True or host_comm)")
         self.ctx, self.n, self.n_frames, self.world, self.rank = ctx, int(n), int(n_frames), int(world), int(rank)
@@ -289,9 +294,18 @@ class TwoChannelBatch:
                 self.refocus_params = dataclasses.replace(refocus, footprint_speed_mps=vg, want_curves=False, want_chips=False)
                 self.refocus_params.validate(self.n)
                 extra = self.refocus_params.record_bytes(self.detect.max_detections)
+            self.cluster_params = cluster
+            if cluster is not None:                                  # the plot records ride behind the refocus records
+                from . import cluster as clu
+                self._cluster_cp = cluster.c_params(self.detect.max_detections)
+                self.plots_offset = self.gmti_bytes + extra
+                extra += clu.plots_bytes(self._cluster_cp)
+                for st in self._lane_state:                          # the detector's own list: a scratch slot per lane
+                    st["reports"] = ctx.alloc(self.gmti_bytes)
             self.slot_shape = ((self.gmti_bytes + extra) // 4,)     # raw bytes, carried as fp32 words by every transport
         else:
             self.detect = None
+            self.cluster_params = None
             self.slot_shape = (n // looks, n // looks) if stack == "multilook" else (n, n) if stack == "magnitude" else (3, n, n)
         self.slot_bytes = int(np.prod(self.slot_shape)) * 4
         self.n_rounds = rounds(self.n_frames, self.world)
@@ -413,7 +427,13 @@ class TwoChannelBatch:
         from . import gmti
         from ._ffi import check
         check(self.ctx.lib.sarx_memset(self.ctx.h, slot_ptr, 0, self.slot_bytes), self.ctx.h)     # no stale bytes past the count
-        gmti.enqueue(self.ctx, dpca_mag.ptr, self.s1.ptr, self.s2.ptr, self.n, self.n, self.detect, 0.0, slot_ptr)
+        if self.cluster_params is None:
+            gmti.enqueue(self.ctx, dpca_mag.ptr, self.s1.ptr, self.s2.ptr, self.n, self.n, self.detect, 0.0, slot_ptr)
+        else:                                               # reports into the lane's scratch slot, plots at the frame's place
+            from . import cluster as clu
+            reports = self._lane_state[self._cur]["reports"].ptr
+            gmti.enqueue(self.ctx, dpca_mag.ptr, self.s1.ptr, self.s2.ptr, self.n, self.n, self.detect, 0.0, reports)
+            clu.enqueue_step(self.ctx, self._cluster_cp, reports, slot_ptr, slot_ptr + self.plots_offset, None)
         if self.refocus_params is not None:
             from . import refocus
             r0, dr = refocus.range_geometry(self.plan.axes()[0])
@@ -433,6 +453,24 @@ class TwoChannelBatch:
         lam, prf, v = self.focus_args[0], self.focus_args[4], self.focus_args[5]
         lag = self.detect.lag_s if self.detect.lag_s is not None else 1.0 / prf
         return gmti.decode_slot(raw, self.detect, ra, ca, lam, v, lag)
+
+    def plots(self, f):
+        """stack="detections" with cluster=: frame f's GmtiPlots, decoded from the plot list and the records behind it (raises
+        GmtiOverflowError if the report list overflowed).  Labels are not shipped (None); n_reports is the number of reports in
+        the kept plots, the sum of their n_members."""
+        from . import cluster as clu, gmti
+        if self.cluster_params is None:
+            raise ValueError("plots() needs cluster=")
+        raw = self.stack([f])[0].view(np.uint8)
+        count, overflow = (int(x) for x in raw[:8].view("<u4"))
+        if overflow or count > self.detect.max_detections:
+            raise gmti.GmtiOverflowError(count, self.detect.max_detections)
+        rec = raw[self.plots_offset:self.plots_offset + count * clu.PLOT_DTYPE.itemsize]
+        ra, ca = self._lane_state[0]["plan"].axes()
+        lam, prf, v = self.focus_args[0], self.focus_args[4], self.focus_args[5]
+        lag = self.detect.lag_s if self.detect.lag_s is not None else 1.0 / prf
+        return clu.GmtiPlots(raw[:self.gmti_bytes], rec, None, int(rec.view(clu.PLOT_DTYPE)["n_members"].sum()), detect=self.detect,
+                             range_axis=ra, cross_range=ca, wavelength_m=lam, platform_speed_mps=v, lag_s=lag)
 
     def refocus(self, f):
         """stack="detections" with refocus=: frame f's RefocusResult, decoded from the records behind its report list (raises
@@ -567,7 +605,7 @@ class TwoChannelBatch:
         for b in (self.d_stack, *(x for pair in self._alloc for x in pair)):
             b.release()
         for st in self._lane_state:
-            for b in (st["s1"], st["s2"], st["masked"], st["d_max"], *st["outs"].values()):
+            for b in (st["s1"], st["s2"], st["masked"], st["d_max"], *st["outs"].values(), *([st["reports"]] if "reports" in st else [])):
                 b.release()
             st["plan"].close()
         if hasattr(self, "d_gmax"):

@@ -265,7 +265,7 @@ def two_channel_workspace(ctx, n_az, n_rg):
 def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp_rate_hzpsec, sample_rate_hz,
                    prf_hz, platform_speed_mps, range_ref_m, t_start_fast, mask_frac=0.05, cal_phase=0.0, *,
                    ctx=None, pulse_shift=True, return_slc2=True, unmasked_phase=False, device_output=False,
-                   workspace=None, fetch_stats=True, detect=None, refocus=None, balance=None, coherence=None):
+                   workspace=None, fetch_stats=True, detect=None, refocus=None, balance=None, coherence=None, cluster=None):
     """The reference script's processing section in one call
     (sar_ati_dcpa_sim_csa.py:402-419,447-449): pulse shift, CSA focus of both
     channels, ATI/DPCA products, 5 % magnitude mask.  Nothing visits the host between the steps; with DeviceArray
@@ -293,6 +293,9 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
                           is downloaded
     refocus             : sarx.RefocusParams (needs detect): the GMTI refocus (sarx.gmti_refocus) runs on this call's device
                           images straight after the detector, on the same lane, and res["refocus"] is its RefocusResult
+    cluster             : sarx.ClusterParams (needs detect): the plot extraction (sarx.gmti_cluster) runs on the report list
+                          straight after the detector, on the same lane; res["detections"] stays the raw report list,
+                          res["plots"] is the GmtiPlots, and a refocus then runs on the PLOT list: one chip per object
     balance             : sarx.BalanceParams: channel 2's image is balanced in place against channel 1's (sarx.channel_balance)
                           on this call's lane once both are focused; the products come from the separate ATI/DPCA launch on the
                           balanced pair with cal_phase = 0 (the azimuth epilogue cannot form them: the weight needs channel 2's
@@ -308,6 +311,9 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
     """
     if refocus is not None and detect is None:
         raise ValueError("refocus needs detect (the report list it refocuses)")
+    if cluster is not None and detect is None:
+        raise ValueError("cluster needs detect (the report list it merges)")
+    cluster_cp = cluster.c_params(detect.max_detections) if cluster is not None else None
     if balance is not None:
         balance.check()
     if coherence is not None:
@@ -405,19 +411,33 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
         if detect is not None:                              # CFAR + refine on the planes of this call; the report list comes back
             from . import gmti
             slot = ctx.alloc(detect.slot_bytes())
-            refocused = None
+            refocused = plots = None
+            held = [slot]
+            lag = detect.lag_s if detect.lag_s is not None else 1.0 / prf_hz
             try:
                 gmti.enqueue(ctx, bufs["dpca_mag"].ptr, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, detect, cal_phase, slot.ptr)
+                target = slot                               # the list the refocus works on: the reports, or the plots
+                if cluster is not None:                     # one launch behind refine on this lane
+                    from . import cluster as clu
+                    md = detect.max_detections
+                    pslot, prec, plab = ctx.alloc(detect.slot_bytes()), ctx.alloc(clu.plots_bytes(cluster_cp)), ctx.alloc(md * 4)
+                    held += [pslot, prec, plab]
+                    clu.enqueue_step(ctx, cluster_cp, slot.ptr, pslot.ptr, prec.ptr, plab.ptr)
+                    target = pslot
                 if refocus is not None:                     # enqueued behind refine on this lane; an overflowed list raises here
                     from .refocus import refocus_slot
-                    refocused = refocus_slot(ctx, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, refocus, ra, slot.ptr,
+                    refocused = refocus_slot(ctx, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, refocus, ra, target.ptr,
                                              detect.max_detections, wavelength_m=center_wavelength_m,
                                              platform_speed_mps=platform_speed_mps, prf_hz=prf_hz, cal_phase=cal_phase)
                 raw = gmti.fetch_slot(ctx, slot.ptr, detect.max_detections)
+                if cluster is not None:
+                    plots = clu.fetch_plots(ctx, pslot.ptr, prec.ptr, plab.ptr, md, in_ptr=slot.ptr, detect=detect, range_axis=ra,
+                                            cross_range=ca, wavelength_m=center_wavelength_m, platform_speed_mps=platform_speed_mps,
+                                            lag_s=lag)
             finally:
-                slot.release()
-            report = gmti.decode_slot(raw, detect, ra, ca, center_wavelength_m, platform_speed_mps,
-                                      detect.lag_s if detect.lag_s is not None else 1.0 / prf_hz)
+                for b in held:
+                    b.release()
+            report = gmti.decode_slot(raw, detect, ra, ca, center_wavelength_m, platform_speed_mps, lag)
         coh_summary = None
         if coherence is not None:                           # on the pair the products came from
             from .coherence import SUMMARY_BYTES, SUMMARY_DTYPE, CoherenceResult, coherence_dev
@@ -436,6 +456,8 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
             res["detections"] = report
         if refocus is not None:
             res["refocus"] = refocused
+        if cluster is not None:
+            res["plots"] = plots
         if balanced is not None:
             res["balance"] = balanced
         names = ["slc1"] + (["slc2"] if (return_slc2 or not fused) else []) + ["slc1_mag", "dpca_mag", "ati_phase_masked"] + \
