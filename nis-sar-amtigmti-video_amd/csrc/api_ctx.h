@@ -1,4 +1,4 @@
-// What the host units of the C ABI share (api_ctx.hip, api_csa.hip, api_focus.hip, api_comm.hip, api_gmti.hip, api_balance.hip, api_track.hip, api_coherence.hip, api_oscfar.hip, api_cluster.hip): the context behind
+// What the host units of the C ABI share (api_ctx.hip, api_csa.hip, api_focus.hip, api_comm.hip, api_gmti.hip, api_balance.hip, api_track.hip, api_coherence.hip, api_oscfar.hip, api_cluster.hip, api_atigate.hip): the context behind
 // sarx_ctx*, error reporting, the exception guard and the staged host copies.  Host only: no kernel file includes this header.
 #pragma once
 #include "../../include/sarx.h"
@@ -68,6 +68,7 @@ struct sarx_ctx {
     size_t gmti_copy_cap[LANES] = {};          // reports it holds
     float* refocus_curves[LANES] = {};         // sarx_refocus_dev without caller curves: the S_k the record launch reads, one per lane
     size_t refocus_curves_cap[LANES] = {};     // floats it holds
+    int32_t* atigate_keep[LANES] = {};         // sarx_atigate_step_dev: the keep flags between its two launches, one set per lane
     std::string err;
 };
 

@@ -312,6 +312,30 @@ CLUSTER_SIGNATURES = {
     "sarx_cluster_run_dev": (_i, [_vp, _P(ClusterParams), _vp, _sz, _vp, _sz, _i, _vp, _sz, _vp]),
 }
 
+# include/sarx_atigate.h: the GMTI ATI gate, a ninth table bound the same way
+ATIGATE_MAX_LOOK, ATIGATE_MAX_DETECTIONS, ATIGATE_KEEP_UNTESTED = 4, 16384, 1  # SARX_ATIGATE_MAX_LOOK, _MAX_DETECTIONS, _KEEP_UNTESTED
+
+
+class AtiGateParams(C.Structure):
+    """sarx_atigate_params (64 bytes)"""
+    _fields_ = [("guard_az", C.c_int32), ("guard_rg", C.c_int32), ("train_az", C.c_int32), ("train_rg", C.c_int32),
+                ("look_az", C.c_int32), ("look_rg", C.c_int32), ("k_sigma", C.c_double), ("phase_min", C.c_double),
+                ("min_coh", C.c_double), ("min_train", C.c_int32), ("max_detections", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class AtiGateStat(C.Structure):
+    """sarx_atigate_stat (96 bytes)"""
+    _fields_ = [(n, C.c_double) for n in ("c11", "c22", "c12_re", "c12_im", "i_re", "i_im", "coh", "psi", "sigma")] + \
+               [(n, C.c_int32) for n in ("n_train", "n_look", "status", "reason", "out_index", "reserved")]
+
+
+ATIGATE_SIGNATURES = {
+    "sarx_atigate_check": (_i, [_P(AtiGateParams)]),
+    "sarx_atigate_stats_bytes": (_i, [_P(AtiGateParams), _P(_sz)]),
+    "sarx_atigate_step_dev": (_i, [_vp, _P(AtiGateParams), _vp, _vp, _i, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -326,7 +350,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
             list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()) + \
-            list(CLUSTER_SIGNATURES.items()):
+            list(CLUSTER_SIGNATURES.items()) + list(ATIGATE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

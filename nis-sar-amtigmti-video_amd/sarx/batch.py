@@ -215,6 +215,9 @@ class TwoChannelBatch:
     With cluster=ClusterParams(...) the detector writes into a scratch slot of the lane and the plot extraction (sarx.cluster) writes
     the PLOT list at the frame's place in the stack, in the same layout: refocus and tracker then work on plots, b.detections(f)
     decodes the plot list, and the plot records ride behind the refocus records (b.plots(f)).  Without cluster= nothing of it exists.
+    With ati_gate=AtiGateParams(...) the ATI gate (sarx.atigate) runs between the detector and the plot extraction: the detector
+    writes into a scratch slot of the lane and the GATED list goes to the frame's place in the stack (or, with cluster=, into a
+    second scratch slot the plot extraction reads).  Only the gated slot is shipped, not the gate's statistics records.
 
     The stack lives in one device buffer [rounds][world][slot]; a frame's slot is produced directly at its place
     and each round is gathered IN PLACE (send = recv + rank * slot), so there is no send buffer to recycle and no
@@ -227,7 +230,7 @@ class TwoChannelBatch:
     def __init__(self, ctx, n, n_frames, world=1, rank=0, stack="multilook", looks=16, rccl=False, host_comm=None,
                  seed_base=1000, flags=None, mask_frac=0.05, resident=True, fused_mask=True, fused_ati=True, scene="noise",
                  scene_scale=1.0, lanes=None, detect=None, refocus=None, track=None,
-                 frame_dt_s=0.1, cluster=None):
+                 frame_dt_s=0.1, cluster=None, ati_gate=None):
         from . import _ffi, radar
         from .engine import CsaPlan
         if stack not in STACKS:
@@ -236,6 +239,8 @@ class TwoChannelBatch:
             raise ValueError('track needs stack="detections"')
         if cluster is not None and stack != "detections":
             raise ValueError('cluster needs stack="detections"')
+        if ati_gate is not None and stack != "detections":
+            raise ValueError('ati_gate needs stack="detections"')
         if world > 1 and not rccl and host_comm is None:
             raise ValueError("world > 1 needs a transport (rccl=True or host_comm)")
         self.ctx, self.n, self.n_frames, self.world, self.rank = ctx, int(n), int(n_frames), int(world), int(rank)
@@ -302,10 +307,19 @@ class TwoChannelBatch:
                 extra += clu.plots_bytes(self._cluster_cp)
                 for st in self._lane_state:                          # the detector's own list: a scratch slot per lane
                     st["reports"] = ctx.alloc(self.gmti_bytes)
+            self.gate_params = ati_gate
+            if ati_gate is not None:
+                self._gate_cp = ati_gate.c_params(self.detect.max_detections)
+                for st in self._lane_state:                          # the detector's list, and the gated one when cluster reads it
+                    if "reports" not in st:
+                        st["reports"] = ctx.alloc(self.gmti_bytes)
+                    if cluster is not None:
+                        st["gated"] = ctx.alloc(self.gmti_bytes)
             self.slot_shape = ((self.gmti_bytes + extra) // 4,)     # raw bytes, carried as fp32 words by every transport
         else:
             self.detect = None
             self.cluster_params = None
+            self.gate_params = None
             self.slot_shape = (n // looks, n // looks) if stack == "multilook" else (n, n) if stack == "magnitude" else (3, n, n)
         self.slot_bytes = int(np.prod(self.slot_shape)) * 4
         self.n_rounds = rounds(self.n_frames, self.world)
@@ -427,13 +441,20 @@ class TwoChannelBatch:
         from . import gmti
         from ._ffi import check
         check(self.ctx.lib.sarx_memset(self.ctx.h, slot_ptr, 0, self.slot_bytes), self.ctx.h)     # no stale bytes past the count
-        if self.cluster_params is None:
+        if self.cluster_params is None and self.gate_params is None:
             gmti.enqueue(self.ctx, dpca_mag.ptr, self.s1.ptr, self.s2.ptr, self.n, self.n, self.detect, 0.0, slot_ptr)
-        else:                                               # reports into the lane's scratch slot, plots at the frame's place
-            from . import cluster as clu
-            reports = self._lane_state[self._cur]["reports"].ptr
+        else:                                               # reports into the lane's scratch slot, the last stage at the frame's place
+            st = self._lane_state[self._cur]
+            reports = st["reports"].ptr
             gmti.enqueue(self.ctx, dpca_mag.ptr, self.s1.ptr, self.s2.ptr, self.n, self.n, self.detect, 0.0, reports)
-            clu.enqueue_step(self.ctx, self._cluster_cp, reports, slot_ptr, slot_ptr + self.plots_offset, None)
+            if self.gate_params is not None:                # the statistics records are not kept
+                from . import atigate as gat
+                gated = st["gated"].ptr if self.cluster_params is not None else slot_ptr
+                gat.enqueue_step(self.ctx, self._gate_cp, self.s1.ptr, self.s2.ptr, self.n, self.n, reports, gated, None)
+                reports = gated
+            if self.cluster_params is not None:
+                from . import cluster as clu
+                clu.enqueue_step(self.ctx, self._cluster_cp, reports, slot_ptr, slot_ptr + self.plots_offset, None)
         if self.refocus_params is not None:
             from . import refocus
             r0, dr = refocus.range_geometry(self.plan.axes()[0])
@@ -605,7 +626,7 @@ class TwoChannelBatch:
         for b in (self.d_stack, *(x for pair in self._alloc for x in pair)):
             b.release()
         for st in self._lane_state:
-            for b in (st["s1"], st["s2"], st["masked"], st["d_max"], *st["outs"].values(), *([st["reports"]] if "reports" in st else [])):
+            for b in (st["s1"], st["s2"], st["masked"], st["d_max"], *st["outs"].values(), *(st[k] for k in ("reports", "gated") if k in st)):
                 b.release()
             st["plan"].close()
         if hasattr(self, "d_gmax"):

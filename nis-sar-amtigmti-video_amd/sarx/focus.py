@@ -265,7 +265,8 @@ def two_channel_workspace(ctx, n_az, n_rg):
 def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp_rate_hzpsec, sample_rate_hz,
                    prf_hz, platform_speed_mps, range_ref_m, t_start_fast, mask_frac=0.05, cal_phase=0.0, *,
                    ctx=None, pulse_shift=True, return_slc2=True, unmasked_phase=False, device_output=False,
-                   workspace=None, fetch_stats=True, detect=None, refocus=None, balance=None, coherence=None, cluster=None):
+                   workspace=None, fetch_stats=True, detect=None, refocus=None, balance=None, coherence=None, cluster=None,
+                   ati_gate=None):
     """The reference script's processing section in one call
     (sar_ati_dcpa_sim_csa.py:402-419,447-449): pulse shift, CSA focus of both
     channels, ATI/DPCA products, 5 % magnitude mask.  Nothing visits the host between the steps; with DeviceArray
@@ -296,6 +297,9 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
     cluster             : sarx.ClusterParams (needs detect): the plot extraction (sarx.gmti_cluster) runs on the report list
                           straight after the detector, on the same lane; res["detections"] stays the raw report list,
                           res["plots"] is the GmtiPlots, and a refocus then runs on the PLOT list: one chip per object
+    ati_gate            : sarx.AtiGateParams (needs detect): the ATI gate (sarx.gmti_ati_gate) runs on the report list straight
+                          after refine, on the same lane, before cluster and refocus, which then work on the gated list;
+                          res["detections"] is the GATED list and carries the statistics of every report that went in as `.gate`
     balance             : sarx.BalanceParams: channel 2's image is balanced in place against channel 1's (sarx.channel_balance)
                           on this call's lane once both are focused; the products come from the separate ATI/DPCA launch on the
                           balanced pair with cal_phase = 0 (the azimuth epilogue cannot form them: the weight needs channel 2's
@@ -314,6 +318,9 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
     if cluster is not None and detect is None:
         raise ValueError("cluster needs detect (the report list it merges)")
     cluster_cp = cluster.c_params(detect.max_detections) if cluster is not None else None
+    if ati_gate is not None and detect is None:
+        raise ValueError("ati_gate needs detect (the report list it gates)")
+    gate_cp = ati_gate.c_params(detect.max_detections) if ati_gate is not None else None
     if balance is not None:
         balance.check()
     if coherence is not None:
@@ -416,6 +423,12 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
             lag = detect.lag_s if detect.lag_s is not None else 1.0 / prf_hz
             try:
                 gmti.enqueue(ctx, bufs["dpca_mag"].ptr, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, detect, cal_phase, slot.ptr)
+                gate = None
+                if ati_gate is not None:                    # two launches behind refine on this lane; the gated slot takes the
+                    from . import atigate as gat            # detector's place for everything after it
+                    full, slot, gstats = slot, ctx.alloc(detect.slot_bytes()), ctx.alloc(gat.stats_bytes(gate_cp))
+                    held += [slot, gstats]
+                    gat.enqueue_step(ctx, gate_cp, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, full.ptr, slot.ptr, gstats.ptr)
                 target = slot                               # the list the refocus works on: the reports, or the plots
                 if cluster is not None:                     # one launch behind refine on this lane
                     from . import cluster as clu
@@ -430,6 +443,8 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
                                              detect.max_detections, wavelength_m=center_wavelength_m,
                                              platform_speed_mps=platform_speed_mps, prf_hz=prf_hz, cal_phase=cal_phase)
                 raw = gmti.fetch_slot(ctx, slot.ptr, detect.max_detections)
+                if ati_gate is not None:
+                    gate = gat.fetch_gate(ctx, full.ptr, gstats.ptr).copy()
                 if cluster is not None:
                     plots = clu.fetch_plots(ctx, pslot.ptr, prec.ptr, plab.ptr, md, in_ptr=slot.ptr, detect=detect, range_axis=ra,
                                             cross_range=ca, wavelength_m=center_wavelength_m, platform_speed_mps=platform_speed_mps,
@@ -438,6 +453,7 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
                 for b in held:
                     b.release()
             report = gmti.decode_slot(raw, detect, ra, ca, center_wavelength_m, platform_speed_mps, lag)
+            report.gate = gate
         coh_summary = None
         if coherence is not None:                           # on the pair the products came from
             from .coherence import SUMMARY_BYTES, SUMMARY_DTYPE, CoherenceResult, coherence_dev

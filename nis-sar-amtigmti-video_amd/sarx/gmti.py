@@ -167,6 +167,7 @@ class GmtiReport:
         self.method = method
         self.rank = None if rank is None else int(rank)
         self.plots = None                    # gmti_detect(cluster=...): the GmtiPlots of this list
+        self.gate = None                     # gmti_detect(ati_gate=...): the statistics of every report that went into the gate
 
     def __len__(self):
         return self.n_found
@@ -252,7 +253,7 @@ def _plane_ptr(ctx, x, n_az, n_rg, dtype, temps):
 
 
 def gmti_detect(slc1, slc2, range_axis, cross_range, *, wavelength_m, platform_speed_mps, lag_s, guard=(2, 2), train=(8, 8),
-                pfa=1e-6, alpha=None, cal_phase=0.0, max_detections=4096, dpca_mag=None, ctx=None, method="ca", os_rank=None, cluster=None):
+                pfa=1e-6, alpha=None, cal_phase=0.0, max_detections=4096, dpca_mag=None, ctx=None, method="ca", os_rank=None, cluster=None, ati_gate=None):
     """Detect movers in a focused two-channel pair and measure their radial speed.
 
     slc1, slc2  : [N_rg x N_az] complex host arrays (sar_focus_csa's views), or device images ([N_az x N_rg] DeviceArray /
@@ -263,11 +264,15 @@ def gmti_detect(slc1, slc2, range_axis, cross_range, *, wavelength_m, platform_s
     method      : "ca" (cell averaging) or "os" (ordered statistic of rank os_rank, None = (3 N_full) // 4)
     cluster     : sarx.ClusterParams: the plot extraction (sarx.gmti_cluster) runs on the report list on the device; the
                   GmtiReport returned (the raw report list, as always) then carries the GmtiPlots as `.plots`
+    ati_gate    : sarx.AtiGateParams: the ATI gate (sarx.gmti_ati_gate) runs on the report list on the device straight after
+                  refine and before `cluster`; the GmtiReport returned is the GATED list and carries the statistics of every
+                  report that went in as `.gate` (atigate.GATE_DTYPE)
     Returns a GmtiReport; raises GmtiOverflowError if more than max_detections cells qualify."""
     from .engine import default_context
     params = GmtiParams(tuple(guard), tuple(train), pfa, alpha, int(max_detections), lag_s, method, os_rank)
     params.resolved()
     cluster_cp = cluster.c_params(params.max_detections) if cluster is not None else None
+    gate_cp = ati_gate.c_params(params.max_detections) if ati_gate is not None else None
     ctx = ctx or getattr(slc1, "ctx", None) or default_context()
     n_rg, n_az = len(range_axis), len(cross_range)
     n = n_az * n_rg
@@ -285,13 +290,19 @@ def gmti_detect(slc1, slc2, range_axis, cross_range, *, wavelength_m, platform_s
         slot = ctx.alloc(params.slot_bytes())
         temps.append(slot)
         enqueue(ctx, pm, p1, p2, n_az, n_rg, params, cal_phase, slot.ptr)
+        md = params.max_detections
+        if gate_cp is not None:                              # two launches behind refine; everything after it takes the gated slot
+            from . import atigate as gat
+            full, slot, gstats = slot, ctx.alloc(params.slot_bytes()), ctx.alloc(gat.stats_bytes(gate_cp))
+            temps += [slot, gstats]
+            gat.enqueue_step(ctx, gate_cp, p1, p2, n_az, n_rg, full.ptr, slot.ptr, gstats.ptr)
         if cluster_cp is not None:
             from . import cluster as clu
-            md = params.max_detections
             pslot, prec, plab = ctx.alloc(params.slot_bytes()), ctx.alloc(clu.plots_bytes(cluster_cp)), ctx.alloc(md * 4)
             temps += [pslot, prec, plab]
             clu.enqueue_step(ctx, cluster_cp, slot.ptr, pslot.ptr, prec.ptr, plab.ptr)
         raw = fetch_slot(ctx, slot.ptr, params.max_detections)
+        gate = gat.fetch_gate(ctx, full.ptr, gstats.ptr).copy() if gate_cp is not None else None
         if cluster_cp is not None:
             plots = clu.fetch_plots(ctx, pslot.ptr, prec.ptr, plab.ptr, md, in_ptr=slot.ptr, detect=params, range_axis=range_axis,
                                     cross_range=cross_range, wavelength_m=wavelength_m, platform_speed_mps=platform_speed_mps,
@@ -302,4 +313,5 @@ def gmti_detect(slc1, slc2, range_axis, cross_range, *, wavelength_m, platform_s
     report = decode_slot(raw, params, range_axis, cross_range, wavelength_m, platform_speed_mps, lag_s)
     if cluster_cp is not None:
         report.plots = plots
+    report.gate = gate
     return report
