@@ -44,11 +44,6 @@ int sarx_atigate_stats_bytes(const sarx_atigate_params* p, size_t* out) {
     return SARX_OK;
 }
 
-static bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
 int sarx_atigate_step_dev(sarx_ctx* c, const sarx_atigate_params* p, const void* d_slc1, const void* d_slc2, int n_az, int n_rg,
                           const void* d_slot_in, void* d_slot_out, void* d_stats) {
     NEED_CTX(c);
@@ -61,13 +56,14 @@ int sarx_atigate_step_dev(sarx_ctx* c, const sarx_atigate_params* p, const void*
         if (((uintptr_t)d_slc1 & 7) || ((uintptr_t)d_slc2 & 7) || ((uintptr_t)d_slot_in & 7) || ((uintptr_t)d_slot_out & 7) ||
             ((uintptr_t)d_stats & 7))
             return fail(c, SARX_ERR_INVALID, "misaligned image, slot or statistics (8-byte alignment)");
-        const size_t slot = sizeof(sarx_gmti_header) + (size_t)p->max_detections * sizeof(sarx_gmti_report);
+        const size_t slot = gmti_slot_bytes(p->max_detections);
         const size_t img = (size_t)n_az * (size_t)n_rg * sizeof(float2);
         const size_t rec = (size_t)p->max_detections * sizeof(sarx_atigate_stat);
-        if (overlap(d_slot_out, slot, d_slot_in, slot) || overlap(d_slot_out, slot, d_slc1, img) || overlap(d_slot_out, slot, d_slc2, img))
+        if (ranges_overlap(d_slot_out, slot, d_slot_in, slot) || ranges_overlap(d_slot_out, slot, d_slc1, img) ||
+            ranges_overlap(d_slot_out, slot, d_slc2, img))
             return fail(c, SARX_ERR_INVALID, "the ATI gate's output slot overlaps an input");
-        if (overlap(d_stats, rec, d_slot_in, slot) || overlap(d_stats, rec, d_slc1, img) || overlap(d_stats, rec, d_slc2, img) ||
-            overlap(d_stats, rec, d_slot_out, slot))
+        if (ranges_overlap(d_stats, rec, d_slot_in, slot) || ranges_overlap(d_stats, rec, d_slc1, img) ||
+            ranges_overlap(d_stats, rec, d_slc2, img) || ranges_overlap(d_stats, rec, d_slot_out, slot))
             return fail(c, SARX_ERR_INVALID, "the ATI gate's statistics overlap an input or the output slot");
         const int L = c->cur_lane;
         if (!c->atigate_keep[L])                                  // once per lane; freed with the context

@@ -27,26 +27,21 @@ int sarx_cluster_plots_bytes(const sarx_cluster_params* p, size_t* out) {
     return SARX_OK;
 }
 
-static bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
 // n_frames >= 1; the strides are checked by the caller
 static int cluster_run(sarx_ctx* c, const sarx_cluster_params* p, const void* d_in, size_t in_stride, void* d_out, size_t out_stride,
                        int n_frames, void* d_plots, size_t plots_stride, int32_t* d_labels) {
     if (!d_in || !d_out) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
     if (((uintptr_t)d_in & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_plots & 7) || ((uintptr_t)d_labels & 3))
         return fail(c, SARX_ERR_INVALID, "misaligned slot, plot records (8-byte alignment) or labels (4-byte alignment)");
-    const size_t slot = sizeof(sarx_gmti_header) + (size_t)p->max_detections * sizeof(sarx_gmti_report);
+    const size_t slot = gmti_slot_bytes(p->max_detections);
     const size_t last = (size_t)(n_frames - 1);
     const size_t in_span = last * in_stride + slot, out_span = last * out_stride + slot;
     const size_t plots_span = last * plots_stride + (size_t)p->max_detections * sizeof(sarx_cluster_plot);
     const size_t labels_span = (size_t)n_frames * p->max_detections * sizeof(int32_t);
-    if (overlap(d_in, in_span, d_out, out_span)) return fail(c, SARX_ERR_INVALID, "cluster input and output slots overlap");
-    if (overlap(d_in, in_span, d_plots, plots_span) || overlap(d_in, in_span, d_labels, labels_span))
+    if (ranges_overlap(d_in, in_span, d_out, out_span)) return fail(c, SARX_ERR_INVALID, "cluster input and output slots overlap");
+    if (ranges_overlap(d_in, in_span, d_plots, plots_span) || ranges_overlap(d_in, in_span, d_labels, labels_span))
         return fail(c, SARX_ERR_INVALID, "cluster plot records or labels overlap the input");
-    if (n_frames == 1 && (overlap(d_out, slot, d_plots, plots_span) || overlap(d_out, slot, d_labels, labels_span)))
+    if (n_frames == 1 && (ranges_overlap(d_out, slot, d_plots, plots_span) || ranges_overlap(d_out, slot, d_labels, labels_span)))
         return fail(c, SARX_ERR_INVALID, "cluster plot records or labels overlap the output slot");
     ClusterArgs a{};
     a.p = *p;
@@ -78,7 +73,7 @@ int sarx_cluster_run_dev(sarx_ctx* c, const sarx_cluster_params* p, const void* 
         const int rc = cluster_check(c, p);
         if (rc != SARX_OK) return rc;
         if (n_frames < 0) return fail(c, SARX_ERR_INVALID, "cluster n_frames must be >= 0");
-        const size_t slot = sizeof(sarx_gmti_header) + (size_t)p->max_detections * sizeof(sarx_gmti_report);
+        const size_t slot = gmti_slot_bytes(p->max_detections);
         if (in_stride_bytes < slot || (in_stride_bytes & 7) || out_stride_bytes < slot || (out_stride_bytes & 7))
             return fail(c, SARX_ERR_INVALID, "cluster slot strides %zu, %zu must be multiples of 8 and at least the slot's %zu bytes",
                         in_stride_bytes, out_stride_bytes, slot);

@@ -36,12 +36,6 @@ int sarx_coherence_workspace_bytes(const sarx_coherence_params* p, int n_az, int
     return SARX_OK;
 }
 
-// [p, p + n) and [q, q + m) share a byte
-static bool overlap(const void* p, size_t n, const void* q, size_t m) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return p && q && n && m && a < b + m && b < a + n;
-}
-
 struct Span {
     const void* p;
     size_t n;
@@ -51,9 +45,9 @@ struct Span {
 static int check_spans(sarx_ctx* c, const Span* in, int n_in, const Span* out, int n_out) {
     for (int o = 0; o < n_out; ++o) {
         for (int i = 0; i < n_in; ++i)
-            if (overlap(out[o].p, out[o].n, in[i].p, in[i].n)) return fail(c, SARX_ERR_INVALID, "coherence: an output overlaps an input");
+            if (ranges_overlap(out[o].p, out[o].n, in[i].p, in[i].n)) return fail(c, SARX_ERR_INVALID, "coherence: an output overlaps an input");
         for (int k = o + 1; k < n_out; ++k)
-            if (overlap(out[o].p, out[o].n, out[k].p, out[k].n)) return fail(c, SARX_ERR_INVALID, "coherence: two outputs overlap");
+            if (ranges_overlap(out[o].p, out[o].n, out[k].p, out[k].n)) return fail(c, SARX_ERR_INVALID, "coherence: two outputs overlap");
     }
     return SARX_OK;
 }

@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <mutex>
 #include <new>
 #include <string>
@@ -105,6 +106,14 @@ hipError_t sync_all_lanes(sarx_ctx* c);
 hipError_t staged_copy(sarx_ctx* c, void* dst, const void* src, size_t bytes, bool to_device, bool narrow = false, bool ordered = true,
                        bool lane_only = false);
 bool is_page_locked(const void* p);
+
+// bytes of a GMTI slot: the header, then max_detections reports (include/sarx_gmti.h)
+inline size_t gmti_slot_bytes(int max_detections) { return sizeof(sarx_gmti_header) + (size_t)max_detections * sizeof(sarx_gmti_report); }
+// [a, a + na) and [b, b + nb) share a byte; a NULL pointer or an empty range overlaps nothing
+inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && na && nb && x < y + nb && y < x + na;
+}
 void comm_release(sarx_ctx* c);          // sarx_destroy's call into api_comm.hip: the communicator goes with the context
 
 }  // namespace sarx

@@ -30,7 +30,7 @@ int sarx_gmti_slot_bytes(const sarx_gmti_params* p, size_t* out) {
     if (!out) return fail(nullptr, SARX_ERR_INVALID, "out_bytes is NULL");
     const int rc = gmti_check_params(nullptr, p);
     if (rc != SARX_OK) return rc;
-    *out = sizeof(sarx_gmti_header) + (size_t)p->max_detections * sizeof(sarx_gmti_report);
+    *out = gmti_slot_bytes(p->max_detections);
     return SARX_OK;
 }
 

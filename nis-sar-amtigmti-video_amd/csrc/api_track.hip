@@ -102,7 +102,7 @@ int sarx_track_run_dev(sarx_ctx* c, const sarx_track_params* p, const void* d_st
         int rc = track_check(c, p);
         if (rc != SARX_OK) return rc;
         if (n_frames < 0) return fail(c, SARX_ERR_INVALID, "track n_frames must be >= 0");
-        const size_t slot = sizeof(sarx_gmti_header) + (size_t)p->max_detections * sizeof(sarx_gmti_report);
+        const size_t slot = gmti_slot_bytes(p->max_detections);
         if (slot_stride_bytes < slot || (slot_stride_bytes & 7))
             return fail(c, SARX_ERR_INVALID, "track slot stride %zu must be a multiple of 8 and at least the slot's %zu bytes", slot_stride_bytes, slot);
         rc = track_buffers(c, d_stack, d_table, d_assoc, d_workspace);

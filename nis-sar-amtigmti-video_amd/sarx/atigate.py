@@ -19,8 +19,9 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _ffi, gmti
+from . import _ffi, gmti, slot as _slot
 from ._ffi import check
+from .slot import slot_bytes   # noqa: F401
 
 GATE_DTYPE = np.dtype([("c11", "<f8"), ("c22", "<f8"), ("c12_re", "<f8"), ("c12_im", "<f8"), ("i_re", "<f8"), ("i_im", "<f8"),
                        ("coh", "<f8"), ("psi", "<f8"), ("sigma", "<f8"), ("n_train", "<i4"), ("n_look", "<i4"), ("status", "<i4"),
@@ -49,13 +50,7 @@ class AtiGateParams:
             (ga, gr), (ta, tr), (la, lr) = ((int(x) for x in v) for v in (self.guard, self.train, self.looks))
         except (TypeError, ValueError):
             raise ValueError("guard, train and looks must be (azimuth, range) pairs") from None
-        if min(ga, gr, ta, tr) < 0:
-            raise ValueError("guard and train half-widths must be >= 0")
-        if ga + ta > _ffi.GMTI_MAX_HALF or gr + tr > _ffi.GMTI_MAX_HALF:
-            raise ValueError(f"guard + train half-widths ({ga + ta}, {gr + tr}) exceed {_ffi.GMTI_MAX_HALF}")
-        nf = gmti.n_full((ga, gr), (ta, tr))
-        if nf < 1:
-            raise ValueError("the training set is empty")
+        *_, nf = gmti.window((ga, gr), (ta, tr))
         if not (0 <= la <= _ffi.ATIGATE_MAX_LOOK and 0 <= lr <= _ffi.ATIGATE_MAX_LOOK):
             raise ValueError(f"looks must lie in 0 .. {_ffi.ATIGATE_MAX_LOOK}")
         if la > ga or lr > gr:
@@ -86,10 +81,6 @@ def stats_bytes(cp):
     return n.value
 
 
-def slot_bytes(max_detections):
-    return gmti.HEADER_BYTES + int(max_detections) * gmti.REPORT_DTYPE.itemsize
-
-
 def enqueue_step(ctx, cp, d_slc1, d_slc2, n_az, n_rg, in_ptr, out_ptr, stats_ptr):
     """The two launches of one frame on the ctx's current lane; only enqueues."""
     check(ctx.lib.sarx_atigate_step_dev(ctx.h, C.byref(cp), d_slc1, d_slc2, int(n_az), int(n_rg), in_ptr, out_ptr, stats_ptr), ctx.h)
@@ -97,13 +88,8 @@ def enqueue_step(ctx, cp, d_slc1, d_slc2, n_az, n_rg, in_ptr, out_ptr, stats_ptr
 
 def fetch_gate(ctx, in_ptr, stats_ptr):
     """The statistics of the reports the input slot at in_ptr counts (blocking) -> GATE_DTYPE array; empty when it overflowed."""
-    hdr = np.empty(gmti.HEADER_BYTES, np.uint8)
-    check(ctx.lib.sarx_memcpy_d2h(ctx.h, hdr.ctypes.data, in_ptr, gmti.HEADER_BYTES), ctx.h)
-    count, overflow = (int(x) for x in hdr[:8].view("<u4"))
-    rec = np.empty(0 if overflow else count * GATE_DTYPE.itemsize, np.uint8)
-    if rec.nbytes:
-        check(ctx.lib.sarx_memcpy_d2h(ctx.h, rec.ctypes.data, stats_ptr, rec.nbytes), ctx.h)
-    return rec.view(GATE_DTYPE)
+    count, overflow = _slot.header(_slot.fetch_header(ctx, in_ptr))
+    return _slot.download(ctx, stats_ptr, 0 if overflow else count * GATE_DTYPE.itemsize).view(GATE_DTYPE)
 
 
 def gmti_ati_gate(reports, slc1, slc2, params=None, *, range_axis=None, cross_range=None, wavelength_m=None, platform_speed_mps=None,
@@ -119,18 +105,9 @@ def gmti_ati_gate(reports, slc1, slc2, params=None, *, range_axis=None, cross_ra
     detect  : the detector's GmtiParams: its max_detections is the slots' capacity (else max_detections, else the list's length)
     Returns (gated, gate): `gated` a GmtiReport when it can be decoded, else the kept reports as an array of gmti.REPORT_DTYPE;
     `gate` one GATE_DTYPE record per input report.  Raises GmtiOverflowError for an overflowing input list."""
-    from . import cluster as clu, track as trk
     from .engine import default_context
     params = params or AtiGateParams()
-    on_device = hasattr(reports, "ptr")
-    if detect is not None:
-        md = int(detect.max_detections)
-    elif max_detections is not None:
-        md = int(max_detections)
-    elif on_device:
-        raise ValueError("a device slot needs detect= or max_detections= (its capacity)")
-    else:
-        md = max(1, clu._count_of(reports))
+    md, stack, on_device = _slot.stage(reports, detect, max_detections, single=True)
     cp = params.c_params(md)
     if range_axis is not None and cross_range is not None:
         n_az, n_rg = len(cross_range), len(range_axis)
@@ -147,25 +124,22 @@ def gmti_ati_gate(reports, slc1, slc2, params=None, *, range_axis=None, cross_ra
         p1 = gmti._plane_ptr(ctx, slc1, n_az, n_rg, np.complex64, temps)
         p2 = gmti._plane_ptr(ctx, slc2, n_az, n_rg, np.complex64, temps)
         if on_device:
-            in_ptr = reports.ptr
+            in_ptr = on_device[0][1]
         else:
-            d_in = ctx.to_device(trk.encode_slot(reports, md))
-            temps.append(d_in)
-            in_ptr = d_in.ptr
+            temps.append(ctx.to_device(stack[0]))
+            in_ptr = temps[-1].ptr
         d_out, d_stats = ctx.alloc(slot_bytes(md)), ctx.alloc(stats_bytes(cp))
         temps += [d_out, d_stats]
         enqueue_step(ctx, cp, p1, p2, n_az, n_rg, in_ptr, d_out.ptr, d_stats.ptr)
-        raw = gmti.fetch_slot(ctx, d_out.ptr, md)
-        count, overflow = (int(x) for x in raw[:8].view("<u4"))
-        if overflow:
-            raise gmti.GmtiOverflowError(count, md)
+        raw = _slot.fetch(ctx, d_out.ptr, md)
+        _slot.raise_if_overflowed(*_slot.header(raw), md, strict=False)
         gate = fetch_gate(ctx, in_ptr, d_stats.ptr).copy()
     finally:
         for b in temps:
             b.release()
     if range_axis is not None and cross_range is not None and None not in (detect, wavelength_m, platform_speed_mps, lag_s):
-        gated = gmti.decode_slot(raw, detect, range_axis, cross_range, wavelength_m, platform_speed_mps, lag_s)
+        gated = _slot.decode(raw, detect, range_axis, cross_range, wavelength_m, platform_speed_mps, lag_s)
         gated.gate = gate
     else:
-        gated = raw[gmti.HEADER_BYTES:].view(gmti.REPORT_DTYPE).copy()
+        gated = _slot.reports(raw).copy()
     return gated, gate

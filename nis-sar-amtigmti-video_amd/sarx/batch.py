@@ -235,12 +235,9 @@ class TwoChannelBatch:
         from .engine import CsaPlan
         if stack not in STACKS:
             raise ValueError(f"stack must be one of {STACKS}")
-        if track is not None and stack != "detections":
-            raise ValueError('track needs stack="detections"')
-        if cluster is not None and stack != "detections":
-            raise ValueError('cluster needs stack="detections"')
-        if ati_gate is not None and stack != "detections":
-            raise ValueError('ati_gate needs stack="detections"')
+        for name, stage in (("track", track), ("cluster", cluster), ("ati_gate", ati_gate)):
+            if stage is not None and stack != "detections":
+                raise ValueError(f'{name} needs stack="detections"')
         if world > 1 and not rccl and host_comm is None:
             raise ValueError("world > 1 needs a transport (rccl=True or host_comm)")
         self.ctx, self.n, self.n_frames, self.world, self.rank = ctx, int(n), int(n_frames), int(world), int(rank)
@@ -299,22 +296,19 @@ class TwoChannelBatch:
                 self.refocus_params = dataclasses.replace(refocus, footprint_speed_mps=vg, want_curves=False, want_chips=False)
                 self.refocus_params.validate(self.n)
                 extra = self.refocus_params.record_bytes(self.detect.max_detections)
-            self.cluster_params = cluster
+            self.cluster_params, self._cluster_cp = cluster, None
             if cluster is not None:                                  # the plot records ride behind the refocus records
                 from . import cluster as clu
                 self._cluster_cp = cluster.c_params(self.detect.max_detections)
                 self.plots_offset = self.gmti_bytes + extra
                 extra += clu.plots_bytes(self._cluster_cp)
-                for st in self._lane_state:                          # the detector's own list: a scratch slot per lane
-                    st["reports"] = ctx.alloc(self.gmti_bytes)
-            self.gate_params = ati_gate
-            if ati_gate is not None:
-                self._gate_cp = ati_gate.c_params(self.detect.max_detections)
-                for st in self._lane_state:                          # the detector's list, and the gated one when cluster reads it
-                    if "reports" not in st:
-                        st["reports"] = ctx.alloc(self.gmti_bytes)
-                    if cluster is not None:
-                        st["gated"] = ctx.alloc(self.gmti_bytes)
+            self.gate_params = ati_gate                              # the gate's statistics records are not kept
+            self._gate = (ati_gate.c_params(self.detect.max_detections), None) if ati_gate is not None else None
+            # every stage but the last writes into a scratch slot of the lane: the detector's list, and the gated one when cluster reads it
+            self._scratch = ("reports", "gated")[:(cluster is not None) + (ati_gate is not None)]
+            for k in self._scratch:
+                for st in self._lane_state:
+                    st[k] = ctx.alloc(self.gmti_bytes)
             self.slot_shape = ((self.gmti_bytes + extra) // 4,)     # raw bytes, carried as fp32 words by every transport
         else:
             self.detect = None
@@ -441,20 +435,10 @@ class TwoChannelBatch:
         from . import gmti
         from ._ffi import check
         check(self.ctx.lib.sarx_memset(self.ctx.h, slot_ptr, 0, self.slot_bytes), self.ctx.h)     # no stale bytes past the count
-        if self.cluster_params is None and self.gate_params is None:
-            gmti.enqueue(self.ctx, dpca_mag.ptr, self.s1.ptr, self.s2.ptr, self.n, self.n, self.detect, 0.0, slot_ptr)
-        else:                                               # reports into the lane's scratch slot, the last stage at the frame's place
-            st = self._lane_state[self._cur]
-            reports = st["reports"].ptr
-            gmti.enqueue(self.ctx, dpca_mag.ptr, self.s1.ptr, self.s2.ptr, self.n, self.n, self.detect, 0.0, reports)
-            if self.gate_params is not None:                # the statistics records are not kept
-                from . import atigate as gat
-                gated = st["gated"].ptr if self.cluster_params is not None else slot_ptr
-                gat.enqueue_step(self.ctx, self._gate_cp, self.s1.ptr, self.s2.ptr, self.n, self.n, reports, gated, None)
-                reports = gated
-            if self.cluster_params is not None:
-                from . import cluster as clu
-                clu.enqueue_step(self.ctx, self._cluster_cp, reports, slot_ptr, slot_ptr + self.plots_offset, None)
+        st = self._lane_state[self._cur]                    # the last stage writes at the frame's place
+        plots = (self._cluster_cp, slot_ptr + self.plots_offset, None) if self._cluster_cp is not None else None
+        gmti.enqueue_chain(self.ctx, dpca_mag.ptr, self.s1.ptr, self.s2.ptr, self.n, self.n, self.detect, 0.0,
+                           [*(st[k].ptr for k in self._scratch), slot_ptr], self._gate, plots)
         if self.refocus_params is not None:
             from . import refocus
             r0, dr = refocus.range_geometry(self.plan.axes()[0])
@@ -466,44 +450,39 @@ class TwoChannelBatch:
     def detections(self, f):
         """stack="detections": frame f's GmtiReport, decoded from the assembled stack (raises GmtiOverflowError if its list
         overflowed).  Axes and radar from the batch's focus; the lag is one pulse unless detect.lag_s says otherwise."""
-        from . import gmti
         if self.detect is None:
             raise ValueError('detections() needs stack="detections"')
-        raw = self.stack([f])[0].view(np.uint8)
+        from . import slot
+        return slot.decode(self.stack([f])[0].view(np.uint8), *self._decode_args())
+
+    def _decode_args(self):
+        """decode_slot's arguments after raw: axes and radar from the batch's focus, the lag one pulse unless detect.lag_s says otherwise."""
+        from . import slot
         ra, ca = self._lane_state[0]["plan"].axes()
         lam, prf, v = self.focus_args[0], self.focus_args[4], self.focus_args[5]
-        lag = self.detect.lag_s if self.detect.lag_s is not None else 1.0 / prf
-        return gmti.decode_slot(raw, self.detect, ra, ca, lam, v, lag)
+        return self.detect, ra, ca, lam, v, slot.lag_of(self.detect, prf)
 
     def plots(self, f):
         """stack="detections" with cluster=: frame f's GmtiPlots, decoded from the plot list and the records behind it (raises
         GmtiOverflowError if the report list overflowed).  Labels are not shipped (None); n_reports is the number of reports in
         the kept plots, the sum of their n_members."""
-        from . import cluster as clu, gmti
+        from . import cluster as clu, slot
         if self.cluster_params is None:
             raise ValueError("plots() needs cluster=")
         raw = self.stack([f])[0].view(np.uint8)
-        count, overflow = (int(x) for x in raw[:8].view("<u4"))
-        if overflow or count > self.detect.max_detections:
-            raise gmti.GmtiOverflowError(count, self.detect.max_detections)
+        count = slot.raise_if_overflowed(*slot.header(raw), self.detect.max_detections, strict=True)
         rec = raw[self.plots_offset:self.plots_offset + count * clu.PLOT_DTYPE.itemsize]
-        ra, ca = self._lane_state[0]["plan"].axes()
-        lam, prf, v = self.focus_args[0], self.focus_args[4], self.focus_args[5]
-        lag = self.detect.lag_s if self.detect.lag_s is not None else 1.0 / prf
-        return clu.GmtiPlots(raw[:self.gmti_bytes], rec, None, int(rec.view(clu.PLOT_DTYPE)["n_members"].sum()), detect=self.detect,
-                             range_axis=ra, cross_range=ca, wavelength_m=lam, platform_speed_mps=v, lag_s=lag)
+        return clu.GmtiPlots(raw[:self.gmti_bytes], rec, None, int(rec.view(clu.PLOT_DTYPE)["n_members"].sum()), *self._decode_args())
 
     def refocus(self, f):
         """stack="detections" with refocus=: frame f's RefocusResult, decoded from the records behind its report list (raises
         GmtiOverflowError if the list overflowed).  V_r is the batch's focus speed, V_g the orbit's footprint speed."""
-        from . import gmti, refocus
+        from . import refocus, slot
         if self.refocus_params is None:
             raise ValueError("refocus() needs refocus=")
         raw = self.stack([f])[0].view(np.uint8)
-        count, overflow = (int(x) for x in raw[:8].view("<u4"))
-        if overflow or count > self.detect.max_detections:
-            raise gmti.GmtiOverflowError(count, self.detect.max_detections)
-        rep = raw[gmti.HEADER_BYTES:gmti.HEADER_BYTES + count * gmti.REPORT_DTYPE.itemsize].view(gmti.REPORT_DTYPE)
+        count = slot.raise_if_overflowed(*slot.header(raw), self.detect.max_detections, strict=True)
+        rep = slot.reports(raw, count)
         rec = raw[self.gmti_bytes:self.gmti_bytes + count * refocus.RECORD_DTYPE.itemsize]
         return refocus.decode(rec, np.stack([rep["i"], rep["j"]], axis=1), self.refocus_params, self.focus_args[5])
 
@@ -560,9 +539,7 @@ class TwoChannelBatch:
         raw = table.download(np.uint8, (table.nbytes,))
         assoc = d_assoc.download(np.int32, (self.n_frames, md))
         stack = self.stack().reshape(self.n_frames, -1).view(np.uint8)
-        ra = self._lane_state[0]["plan"].axes()[0]
-        lam, prf = self.focus_args[0], self.focus_args[4]
-        lag = self.detect.lag_s if self.detect.lag_s is not None else 1.0 / prf
+        _, ra, _, lam, _, lag = self._decode_args()
         dr = float(ra[-1] - ra[0]) / (len(ra) - 1)
         return trk.TrackResult(raw, assoc, [trk._slot_ij(stack[f], md) for f in range(self.n_frames)], self.frame_dt_s, dr, lam / (4.0 * lag))
 

@@ -18,8 +18,9 @@ from typing import Tuple
 
 import numpy as np
 
-from . import _ffi, gmti
+from . import _ffi, slot as _slot
 from ._ffi import check
+from .slot import count_of, slot_bytes   # noqa: F401
 
 PLOT_DTYPE = np.dtype([("n_members", "<i4"), ("peak_report", "<i4"), ("i_min", "<i4"), ("i_max", "<i4"), ("j_min", "<i4"),
                        ("j_max", "<i4"), ("sum_power", "<f8"), ("centroid_i", "<f8"), ("centroid_j", "<f8"), ("max_ratio", "<f8"),
@@ -60,10 +61,6 @@ def plots_bytes(cp):
     return n.value
 
 
-def slot_bytes(max_detections):
-    return gmti.HEADER_BYTES + int(max_detections) * gmti.REPORT_DTYPE.itemsize
-
-
 def enqueue_step(ctx, cp, in_ptr, out_ptr, plots_ptr, labels_ptr):
     """One frame's launch on the ctx's current lane; only enqueues."""
     check(ctx.lib.sarx_cluster_step_dev(ctx.h, C.byref(cp), in_ptr, out_ptr, plots_ptr, labels_ptr), ctx.h)
@@ -85,11 +82,10 @@ class GmtiPlots:
     def __init__(self, raw, plots_raw, labels, n_reports, detect=None, range_axis=None, cross_range=None, wavelength_m=None,
                  platform_speed_mps=None, lag_s=None):
         raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
-        count, overflow = (int(x) for x in raw[:8].view("<u4"))
-        if overflow:
-            raise gmti.GmtiOverflowError(count, (detect.max_detections if detect is not None else count))
+        count, overflow = _slot.header(raw)
+        _slot.raise_if_overflowed(count, overflow, detect.max_detections if detect is not None else count, strict=False)
         self.raw, self.n_plots, self.n_reports = raw[:slot_bytes(count)], count, int(n_reports)
-        self.reports = self.raw[gmti.HEADER_BYTES:].view(gmti.REPORT_DTYPE)
+        self.reports = _slot.reports(self.raw, count)
         rec = np.ascontiguousarray(plots_raw).view(np.uint8).reshape(-1)[:count * PLOT_DTYPE.itemsize].view(PLOT_DTYPE)
         self.labels = None if labels is None else np.asarray(labels, np.int32)[:self.n_reports].copy()
         have_axes = range_axis is not None and cross_range is not None
@@ -107,7 +103,7 @@ class GmtiPlots:
             self.plots = rec.copy()
         self.detections = None
         if have_axes and None not in (detect, wavelength_m, platform_speed_mps, lag_s):
-            self.detections = gmti.decode_slot(self.raw, detect, range_axis, cross_range, wavelength_m, platform_speed_mps, lag_s)
+            self.detections = _slot.decode(self.raw, detect, range_axis, cross_range, wavelength_m, platform_speed_mps, lag_s)
 
     def __len__(self):
         return self.n_plots
@@ -116,34 +112,16 @@ class GmtiPlots:
         return f"GmtiPlots({self.n_plots} plots of {self.n_reports} reports)"
 
 
-def fetch_plots(ctx, out_ptr, plots_ptr, labels_ptr, max_detections, n_reports=None, in_ptr=None, **decode):
+def fetch_plots(ctx, out_ptr, plots_ptr, labels_ptr, max_detections, n_reports=None, in_ptr=None, decode=()):
     """Download one frame's plot slot, the records it counts and (labels_ptr not None) its labels (blocking) -> GmtiPlots.
-    n_reports is read from the input slot at in_ptr when it is not given."""
-    raw = gmti.fetch_slot(ctx, out_ptr, max_detections)
-    count, overflow = (int(x) for x in raw[:8].view("<u4"))
-    if overflow:
-        raise gmti.GmtiOverflowError(count, max_detections)
+    n_reports is read from the input slot at in_ptr when it is not given; decode: GmtiPlots' arguments after it."""
+    raw = _slot.fetch(ctx, out_ptr, max_detections)
+    count = _slot.raise_if_overflowed(*_slot.header(raw), max_detections, strict=False)
     if n_reports is None:
-        hdr = np.empty(gmti.HEADER_BYTES, np.uint8)
-        check(ctx.lib.sarx_memcpy_d2h(ctx.h, hdr.ctypes.data, in_ptr, gmti.HEADER_BYTES), ctx.h)
-        n_reports = int(hdr.view("<u4")[0])
-    rec = np.empty(count * PLOT_DTYPE.itemsize, np.uint8)
-    if count:
-        check(ctx.lib.sarx_memcpy_d2h(ctx.h, rec.ctypes.data, plots_ptr, rec.nbytes), ctx.h)
-    labels = None
-    if labels_ptr is not None:
-        labels = np.empty(max_detections, np.int32)
-        check(ctx.lib.sarx_memcpy_d2h(ctx.h, labels.ctypes.data, labels_ptr, labels.nbytes), ctx.h)
-    return GmtiPlots(raw, rec, labels, n_reports, **decode)
-
-
-def _count_of(x):
-    if isinstance(x, gmti.GmtiReport):
-        return len(x.detections)
-    a = np.asarray(x)
-    if a.dtype == gmti.REPORT_DTYPE:
-        return len(a)
-    return int(np.ascontiguousarray(a).view(np.uint8).reshape(-1)[:4].view("<u4")[0])
+        n_reports = _slot.header(_slot.fetch_header(ctx, in_ptr))[0]
+    rec = _slot.download(ctx, plots_ptr, count * PLOT_DTYPE.itemsize)
+    labels = _slot.download(ctx, labels_ptr, max_detections * 4).view(np.int32) if labels_ptr is not None else None
+    return GmtiPlots(raw, rec, labels, n_reports, *decode)
 
 
 def gmti_cluster(reports, params=None, *, range_axis=None, cross_range=None, wavelength_m=None, platform_speed_mps=None, lag_s=None,
@@ -158,43 +136,27 @@ def gmti_cluster(reports, params=None, *, range_axis=None, cross_range=None, wav
               and with range_axis, cross_range, wavelength_m, platform_speed_mps and lag_s the plot list is decoded by
               gmti.decode_slot into GmtiPlots.detections.
     Returns a GmtiPlots, or a list of them for a list; raises GmtiOverflowError for an overflowing input list."""
-    from . import track as trk
     from .engine import default_context
     params = params or ClusterParams()
     many = isinstance(reports, (list, tuple))
-    items = list(reports) if many else [reports]
-    host = [x for x in items if not hasattr(x, "ptr")]
-    if detect is not None:
-        md = int(detect.max_detections)
-    elif max_detections is not None:
-        md = int(max_detections)
-    else:
-        if len(host) != len(items):
-            raise ValueError("device slots need detect= or max_detections= (their capacity)")
-        md = max([1] + [_count_of(x) for x in host])
+    md, stack, on_device = _slot.stage(reports, detect, max_detections)
     cp = params.c_params(md)
     ctx = ctx or default_context()
-    n, slot, rec = len(items), slot_bytes(md), plots_bytes(cp)
+    n, slot, rec = len(stack), slot_bytes(md), plots_bytes(cp)
     if n == 0:
         return []
-    decode = dict(detect=detect, range_axis=range_axis, cross_range=cross_range, wavelength_m=wavelength_m,
-                  platform_speed_mps=platform_speed_mps, lag_s=lag_s)
-    stack = np.zeros((n, slot), np.uint8)
-    for f, x in enumerate(items):
-        if not hasattr(x, "ptr"):
-            stack[f] = trk.encode_slot(x, md)
+    decode = (detect, range_axis, cross_range, wavelength_m, platform_speed_mps, lag_s)
     bufs = [ctx.to_device(stack), ctx.alloc(n * slot), ctx.alloc(n * rec), ctx.alloc(n * md * 4)]
     try:
         d_in, d_out, d_plots, d_labels = bufs
-        for f, x in enumerate(items):
-            if hasattr(x, "ptr"):
-                check(ctx.lib.sarx_memcpy_d2d(ctx.h, d_in.ptr + f * slot, x.ptr, slot), ctx.h)
+        for f, ptr in on_device:
+            check(ctx.lib.sarx_memcpy_d2d(ctx.h, d_in.ptr + f * slot, ptr, slot), ctx.h)
         if many:
             enqueue_run(ctx, cp, d_in.ptr, slot, d_out.ptr, slot, n, d_plots.ptr, rec, d_labels.ptr)
         else:
             enqueue_step(ctx, cp, d_in.ptr, d_out.ptr, d_plots.ptr, d_labels.ptr)
         out = [fetch_plots(ctx, d_out.ptr + f * slot, d_plots.ptr + f * rec, d_labels.ptr + f * md * 4, md, in_ptr=d_in.ptr + f * slot,
-                           **decode) for f in range(n)]
+                           decode=decode) for f in range(n)]
     finally:
         for b in bufs:
             b.release()

@@ -313,13 +313,10 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
                           fetched unless device_output is set with fetch_stats=False).  Channel 2's image is kept on the device
                           for it even with return_slc2=False, but not returned
     """
-    if refocus is not None and detect is None:
-        raise ValueError("refocus needs detect (the report list it refocuses)")
-    if cluster is not None and detect is None:
-        raise ValueError("cluster needs detect (the report list it merges)")
+    for name, stage, verb in (("refocus", refocus, "refocuses"), ("cluster", cluster, "merges"), ("ati_gate", ati_gate, "gates")):
+        if stage is not None and detect is None:
+            raise ValueError(f"{name} needs detect (the report list it {verb})")
     cluster_cp = cluster.c_params(detect.max_detections) if cluster is not None else None
-    if ati_gate is not None and detect is None:
-        raise ValueError("ati_gate needs detect (the report list it gates)")
     gate_cp = ati_gate.c_params(detect.max_detections) if ati_gate is not None else None
     if balance is not None:
         balance.check()
@@ -417,43 +414,15 @@ def focus_ati_dpca(raw_rx1, raw_rx2, center_wavelength_m, pulse_width_sec, chirp
         report = None
         if detect is not None:                              # CFAR + refine on the planes of this call; the report list comes back
             from . import gmti
-            slot = ctx.alloc(detect.slot_bytes())
-            refocused = plots = None
-            held = [slot]
-            lag = detect.lag_s if detect.lag_s is not None else 1.0 / prf_hz
-            try:
-                gmti.enqueue(ctx, bufs["dpca_mag"].ptr, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, detect, cal_phase, slot.ptr)
-                gate = None
-                if ati_gate is not None:                    # two launches behind refine on this lane; the gated slot takes the
-                    from . import atigate as gat            # detector's place for everything after it
-                    full, slot, gstats = slot, ctx.alloc(detect.slot_bytes()), ctx.alloc(gat.stats_bytes(gate_cp))
-                    held += [slot, gstats]
-                    gat.enqueue_step(ctx, gate_cp, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, full.ptr, slot.ptr, gstats.ptr)
-                target = slot                               # the list the refocus works on: the reports, or the plots
-                if cluster is not None:                     # one launch behind refine on this lane
-                    from . import cluster as clu
-                    md = detect.max_detections
-                    pslot, prec, plab = ctx.alloc(detect.slot_bytes()), ctx.alloc(clu.plots_bytes(cluster_cp)), ctx.alloc(md * 4)
-                    held += [pslot, prec, plab]
-                    clu.enqueue_step(ctx, cluster_cp, slot.ptr, pslot.ptr, prec.ptr, plab.ptr)
-                    target = pslot
-                if refocus is not None:                     # enqueued behind refine on this lane; an overflowed list raises here
-                    from .refocus import refocus_slot
-                    refocused = refocus_slot(ctx, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, refocus, ra, target.ptr,
-                                             detect.max_detections, wavelength_m=center_wavelength_m,
-                                             platform_speed_mps=platform_speed_mps, prf_hz=prf_hz, cal_phase=cal_phase)
-                raw = gmti.fetch_slot(ctx, slot.ptr, detect.max_detections)
-                if ati_gate is not None:
-                    gate = gat.fetch_gate(ctx, full.ptr, gstats.ptr).copy()
-                if cluster is not None:
-                    plots = clu.fetch_plots(ctx, pslot.ptr, prec.ptr, plab.ptr, md, in_ptr=slot.ptr, detect=detect, range_axis=ra,
-                                            cross_range=ca, wavelength_m=center_wavelength_m, platform_speed_mps=platform_speed_mps,
-                                            lag_s=lag)
-            finally:
-                for b in held:
-                    b.release()
-            report = gmti.decode_slot(raw, detect, ra, ca, center_wavelength_m, platform_speed_mps, lag)
-            report.gate = gate
+            from .refocus import refocus_slot
+            # the refocus works on the chain's last list (reports, gated reports or plots), behind it on this lane and before the
+            # downloads; an overflowed list raises there
+            then = refocus and (lambda target: refocus_slot(
+                ctx, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, refocus, ra, target, detect.max_detections,
+                wavelength_m=center_wavelength_m, platform_speed_mps=platform_speed_mps, prf_hz=prf_hz, cal_phase=cal_phase))
+            report, plots, refocused = gmti.run_chain(
+                ctx, bufs["dpca_mag"].ptr, bufs["slc1"].ptr, bufs["slc2"].ptr, n_az, n_rg, cal_phase, gate_cp, cluster_cp,
+                (detect, ra, ca, center_wavelength_m, platform_speed_mps, gmti.lag_of(detect, prf_hz)), then)
         coh_summary = None
         if coherence is not None:                           # on the pair the products came from
             from .coherence import SUMMARY_BYTES, SUMMARY_DTYPE, CoherenceResult, coherence_dev

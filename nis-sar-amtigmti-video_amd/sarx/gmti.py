@@ -23,29 +23,30 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _ffi
-from ._ffi import SarxError, check
-
-HEADER_BYTES = C.sizeof(_ffi.GmtiHeader)
-REPORT_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("power", "<f8"), ("mean", "<f8"), ("interf_re", "<f8"),
-                         ("interf_im", "<f8"), ("mag1", "<f4"), ("mag2", "<f4")])
-DETECTION_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("range_m", "<f8"), ("cross_range_m", "<f8"), ("power", "<f8"),
-                            ("mean", "<f8"), ("snr_db", "<f8"), ("interf", "<c16"), ("ati_phase", "<f8"), ("v_los_mps", "<f8"),
-                            ("cross_range_relocated_m", "<f8"), ("mag1", "<f4"), ("mag2", "<f4")])
-assert REPORT_DTYPE.itemsize == C.sizeof(_ffi.GmtiReport) == 48
-
-
-class GmtiOverflowError(SarxError):
-    """More cells qualified than the report list holds: the list is never returned truncated."""
-
-    def __init__(self, count, max_detections):
-        super().__init__(-1, f"GMTI: {count} cells qualify, more than max_detections={max_detections}")
-        self.count, self.max_detections = int(count), int(max_detections)
+from ._ffi import check
+from .batch import _Ptr
+# the slot's layout, its errors and its decoded form live in slot.py; these names stay importable from here
+from .slot import (DETECTION_DTYPE, HEADER_BYTES, REPORT_DTYPE, GmtiOverflowError, GmtiReport, decode as decode_slot,   # noqa: F401
+                   fetch as fetch_slot, lag_of, slot_bytes)
 
 
 def n_full(guard, train):
     """Training cells of a window that lies wholly inside the image."""
     (ga, gr), (ta, tr) = guard, train
     return (2 * (ga + ta) + 1) * (2 * (gr + tr) + 1) - (2 * ga + 1) * (2 * gr + 1)
+
+
+def window(guard, train):
+    """The (azimuth, range) half-widths of a guard box and the training ring around it, checked -> ga, gr, ta, tr, N_full."""
+    (ga, gr), (ta, tr) = ((int(x) for x in v) for v in (guard, train))
+    if min(ga, gr, ta, tr) < 0:
+        raise ValueError("guard and train half-widths must be >= 0")
+    if ga + ta > _ffi.GMTI_MAX_HALF or gr + tr > _ffi.GMTI_MAX_HALF:
+        raise ValueError(f"guard + train half-widths ({ga + ta}, {gr + tr}) exceed {_ffi.GMTI_MAX_HALF}")
+    nf = n_full((ga, gr), (ta, tr))
+    if nf < 1:
+        raise ValueError("the training set is empty")
+    return ga, gr, ta, tr, nf
 
 
 def cfar_alpha(pfa, n):
@@ -115,15 +116,7 @@ class GmtiParams:
         return rank
 
     def resolved(self):
-        ga, gr = (int(x) for x in self.guard)
-        ta, tr = (int(x) for x in self.train)
-        if min(ga, gr, ta, tr) < 0:
-            raise ValueError("guard and train half-widths must be >= 0")
-        if ga + ta > _ffi.GMTI_MAX_HALF or gr + tr > _ffi.GMTI_MAX_HALF:
-            raise ValueError(f"guard + train half-widths ({ga + ta}, {gr + tr}) exceed {_ffi.GMTI_MAX_HALF}")
-        nf = n_full((ga, gr), (ta, tr))
-        if nf < 1:
-            raise ValueError("the training set is empty")
+        ga, gr, ta, tr, nf = window(self.guard, self.train)
         rank = self.rank()
         if self.alpha is not None:
             alpha = float(self.alpha)
@@ -145,40 +138,9 @@ class GmtiParams:
         return base if self.method == "ca" else _ffi.OscfarParams(base, self.rank(), 0)
 
     def slot_bytes(self):
-        """Bytes of one device slot: header + max_detections reports (sarx_gmti_slot_bytes)."""
-        cp = self._base_params()
-        n = C.c_size_t()
-        lib = _ffi.load()
-        check(lib.sarx_gmti_slot_bytes(C.byref(cp), C.byref(n)))
-        return n.value
-
-
-class GmtiReport:
-    """Result of a detection: `detections` (structured array, DETECTION_DTYPE, sorted by (i, j)), `n_found`, the `alpha` used, the
-    unambiguous radial speed `v_ambiguity_mps` = lambda / (4 lag), the `method` ("ca" / "os") and, for "os", the `rank` (else
-    None).  With "os" the `mean` field is the ordered statistic x_(rank), so `snr_db` is power over that level."""
-
-    def __init__(self, detections, alpha, v_ambiguity_mps, n_full_cells, method="ca", rank=None):
-        self.detections = detections
-        self.n_found = int(len(detections))
-        self.alpha = float(alpha)
-        self.v_ambiguity_mps = float(v_ambiguity_mps)
-        self.n_full = int(n_full_cells)
-        self.method = method
-        self.rank = None if rank is None else int(rank)
-        self.plots = None                    # gmti_detect(cluster=...): the GmtiPlots of this list
-        self.gate = None                     # gmti_detect(ati_gate=...): the statistics of every report that went into the gate
-
-    def __len__(self):
-        return self.n_found
-
-    def __repr__(self):
-        return f"GmtiReport(n_found={self.n_found}, alpha={self.alpha:.4g}, v_ambiguity_mps={self.v_ambiguity_mps:.4g})"
-
-
-class _Ptr:
-    def __init__(self, ptr):
-        self.ptr = ptr
+        """Bytes of one device slot: header + max_detections reports (what sarx_gmti_slot_bytes answers)."""
+        self.resolved()
+        return slot_bytes(self.max_detections)
 
 
 def enqueue(ctx, d_mag, d_slc1, d_slc2, n_az, n_rg, params, cal_phase, slot_ptr):
@@ -191,43 +153,59 @@ def enqueue(ctx, d_mag, d_slc1, d_slc2, n_az, n_rg, params, cal_phase, slot_ptr)
                                        slot_ptr, int(params.max_detections)), ctx.h)
 
 
-def fetch_slot(ctx, slot_ptr, max_detections):
-    """Header, then the reports it counts (blocking): the raw bytes of a slot, trimmed to its content."""
-    hdr = np.empty(HEADER_BYTES, np.uint8)
-    check(ctx.lib.sarx_memcpy_d2h(ctx.h, hdr.ctypes.data, slot_ptr, HEADER_BYTES), ctx.h)
-    count = int(hdr.view("<u4")[0])
-    n = min(count, int(max_detections))
-    raw = np.empty(HEADER_BYTES + n * REPORT_DTYPE.itemsize, np.uint8)
-    raw[:HEADER_BYTES] = hdr
-    if n:
-        check(ctx.lib.sarx_memcpy_d2h(ctx.h, raw[HEADER_BYTES:].ctypes.data, slot_ptr + HEADER_BYTES, n * REPORT_DTYPE.itemsize), ctx.h)
-    return raw
+def enqueue_chain(ctx, d_mag, d_slc1, d_slc2, n_az, n_rg, params, cal_phase, slots, gate=None, cluster=None):
+    """The chain in its fixed order on the ctx's current lane: detect (CFAR or OS-CFAR, refine), the ATI gate when `gate` =
+    (its c_params, statistics pointer or None) is given, the plot extraction when `cluster` = (its c_params, plot records pointer,
+    labels pointer or None) is given.  `slots`: one slot pointer per stage that runs, in that order - every stage reads the slot of
+    the stage before it and writes its own.  Returns the last slot written, the one refocus, tracker or fetch read next.  The caller
+    owns every buffer; only enqueues."""
+    from . import atigate, cluster as clu
+    slots = iter(slots)
+    cur = next(slots)
+    enqueue(ctx, d_mag, d_slc1, d_slc2, n_az, n_rg, params, cal_phase, cur)
+    if gate is not None:
+        src, cur = cur, next(slots)
+        atigate.enqueue_step(ctx, gate[0], d_slc1, d_slc2, n_az, n_rg, src, cur, gate[1])
+    if cluster is not None:
+        src, cur = cur, next(slots)
+        clu.enqueue_step(ctx, cluster[0], src, cur, cluster[1], cluster[2])
+    return cur
 
 
-def decode_slot(raw, params, range_axis, cross_range, wavelength_m, platform_speed_mps, lag_s):
-    """A slot's bytes (header + reports) -> GmtiReport.  Raises GmtiOverflowError when the list overflowed."""
-    raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
-    count, overflow = (int(x) for x in raw[:8].view("<u4"))
-    if overflow or count > params.max_detections:
-        raise GmtiOverflowError(count, params.max_detections)
-    rep = raw[HEADER_BYTES:HEADER_BYTES + count * REPORT_DTYPE.itemsize].view(REPORT_DTYPE)
-    _, _, _, _, nf, alpha = params.resolved()
-    lam, lag = float(wavelength_m), float(lag_s)
-    out = np.zeros(count, DETECTION_DTYPE)
-    ra, ca = np.asarray(range_axis, dtype=np.float64), np.asarray(cross_range, dtype=np.float64)
-    for k in ("i", "j", "power", "mean", "mag1", "mag2"):
-        out[k] = rep[k]
-    out["range_m"] = ra[rep["j"]]
-    out["cross_range_m"] = ca[rep["i"]]
-    with np.errstate(divide="ignore"):
-        out["snr_db"] = 10.0 * np.log10(rep["power"] / rep["mean"])
-    out["interf"] = rep["interf_re"] + 1j * rep["interf_im"]
-    out["ati_phase"] = np.angle(out["interf"])
-    # slc1 (Rx1[1:]) sees the scene one lag after slc2 (Rx2[:-1]) from the same phase centre: a receding target (v_los > 0) is
-    # further away for slc1, so angle(slc1 conj(slc2)) = -4 pi v_los lag / lambda; it is imaged R v_los / V earlier in azimuth
-    out["v_los_mps"] = -lam * out["ati_phase"] / (4.0 * math.pi * lag)
-    out["cross_range_relocated_m"] = out["cross_range_m"] + out["range_m"] * out["v_los_mps"] / float(platform_speed_mps)
-    return GmtiReport(out, alpha, lam / (4.0 * lag), nf, params.method, params.rank())
+def run_chain(ctx, d_mag, d_slc1, d_slc2, n_az, n_rg, cal_phase, gate_cp, cluster_cp, decode, then=None):
+    """The chain for a caller that keeps no slots (gmti_detect, focus_ati_dpca): temporaries for every stage (a slot each, the gate's
+    statistics, the plot records and labels), enqueue_chain, `then`(the last slot's pointer) while they live - focus_ati_dpca's
+    refocus -, and the downloads (blocking).  decode: decode_slot's arguments after raw.  Returns the GmtiReport of the detector's
+    list - with a gate the gated one, the statistics as its .gate -, the GmtiPlots or None, and what `then` returned."""
+    from . import atigate, cluster as clu
+    params, held = decode[0], []
+    md, size = params.max_detections, params.slot_bytes()
+
+    def alloc(nbytes):
+        held.append(ctx.alloc(nbytes))
+        return held[-1].ptr
+    try:
+        slots, gate, cluster, stats, plots = [alloc(size)], None, None, None, None
+        if gate_cp is not None:
+            slots.append(alloc(size))
+            gate = (gate_cp, alloc(atigate.stats_bytes(gate_cp)))
+        if cluster_cp is not None:
+            slots.append(alloc(size))
+            cluster = (cluster_cp, alloc(clu.plots_bytes(cluster_cp)), alloc(md * 4))
+        last = enqueue_chain(ctx, d_mag, d_slc1, d_slc2, n_az, n_rg, params, cal_phase, slots, gate, cluster)
+        extra = then(last) if then else None
+        out = slots[0] if gate is None else slots[1]
+        raw = fetch_slot(ctx, out, md)
+        if gate is not None:
+            stats = atigate.fetch_gate(ctx, slots[0], gate[1]).copy()
+        if cluster is not None:
+            plots = clu.fetch_plots(ctx, last, cluster[1], cluster[2], md, in_ptr=out, decode=decode)
+    finally:
+        for b in held:
+            b.release()
+    report = decode_slot(raw, *decode)
+    report.gate = stats
+    return report, plots, extra
 
 
 def _plane_ptr(ctx, x, n_az, n_rg, dtype, temps):
@@ -287,31 +265,9 @@ def gmti_detect(slc1, slc2, range_axis, cross_range, *, wavelength_m, platform_s
             pm = outs["dpca_mag"].ptr
         else:
             pm = _plane_ptr(ctx, dpca_mag, n_az, n_rg, np.float32, temps)
-        slot = ctx.alloc(params.slot_bytes())
-        temps.append(slot)
-        enqueue(ctx, pm, p1, p2, n_az, n_rg, params, cal_phase, slot.ptr)
-        md = params.max_detections
-        if gate_cp is not None:                              # two launches behind refine; everything after it takes the gated slot
-            from . import atigate as gat
-            full, slot, gstats = slot, ctx.alloc(params.slot_bytes()), ctx.alloc(gat.stats_bytes(gate_cp))
-            temps += [slot, gstats]
-            gat.enqueue_step(ctx, gate_cp, p1, p2, n_az, n_rg, full.ptr, slot.ptr, gstats.ptr)
-        if cluster_cp is not None:
-            from . import cluster as clu
-            pslot, prec, plab = ctx.alloc(params.slot_bytes()), ctx.alloc(clu.plots_bytes(cluster_cp)), ctx.alloc(md * 4)
-            temps += [pslot, prec, plab]
-            clu.enqueue_step(ctx, cluster_cp, slot.ptr, pslot.ptr, prec.ptr, plab.ptr)
-        raw = fetch_slot(ctx, slot.ptr, params.max_detections)
-        gate = gat.fetch_gate(ctx, full.ptr, gstats.ptr).copy() if gate_cp is not None else None
-        if cluster_cp is not None:
-            plots = clu.fetch_plots(ctx, pslot.ptr, prec.ptr, plab.ptr, md, in_ptr=slot.ptr, detect=params, range_axis=range_axis,
-                                    cross_range=cross_range, wavelength_m=wavelength_m, platform_speed_mps=platform_speed_mps,
-                                    lag_s=lag_s)
+        report, report.plots, _ = run_chain(ctx, pm, p1, p2, n_az, n_rg, cal_phase, gate_cp, cluster_cp,
+                                            (params, range_axis, cross_range, wavelength_m, platform_speed_mps, lag_s))
     finally:
         for b in temps:
             b.release()
-    report = decode_slot(raw, params, range_axis, cross_range, wavelength_m, platform_speed_mps, lag_s)
-    if cluster_cp is not None:
-        report.plots = plots
-    report.gate = gate
     return report

@@ -19,9 +19,9 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, slot as _slot
 from ._ffi import check
-from .gmti import HEADER_BYTES, REPORT_DTYPE, GmtiOverflowError, GmtiReport, _plane_ptr
+from .gmti import HEADER_BYTES, REPORT_DTYPE, GmtiOverflowError, GmtiReport, _plane_ptr   # noqa: F401
 
 RECORD_DTYPE = np.dtype([("k_best", "<i4"), ("i0", "<i4"), ("peak_i", "<i4"), ("peak_j", "<i4"), ("s_prev", "<f4"), ("s_best", "<f4"),
                          ("s_next", "<f4"), ("s_identity", "<f4"), ("peak_power", "<f4"), ("orig_power", "<f4"), ("reserved", "<i4", (2,))])
@@ -161,13 +161,6 @@ def enqueue(ctx, d_slc1, d_slc2, n_az, n_rg, cparams, slot_ptr, max_detections, 
                                    int(max_detections), d_records, d_curves, d_chips), ctx.h)
 
 
-def _d2h(ctx, ptr, nbytes):
-    out = np.empty(int(nbytes), np.uint8)
-    if nbytes:
-        check(ctx.lib.sarx_memcpy_d2h(ctx.h, out.ctypes.data, ptr, int(nbytes)), ctx.h)
-    return out
-
-
 class _Outputs:
     """Device buffers of one refocus call: records, and curves / chips when requested."""
 
@@ -183,9 +176,9 @@ class _Outputs:
         return self.rec.ptr, (self.curves.ptr if self.curves else None), (self.chips.ptr if self.chips else None)
 
     def fetch(self, ctx, n):
-        rec = _d2h(ctx, self.rec.ptr, n * RECORD_DTYPE.itemsize).view(RECORD_DTYPE)
-        curves = _d2h(ctx, self.curves.ptr, n * self.n_hyp * 4).view(np.float32).reshape(n, self.n_hyp) if self.curves else None
-        chips = _d2h(ctx, self.chips.ptr, n * self.L * self.W * 8).view(np.complex64).reshape(n, self.L, self.W) if self.chips else None
+        rec = _slot.download(ctx, self.rec.ptr, n * RECORD_DTYPE.itemsize).view(RECORD_DTYPE)
+        curves = _slot.download(ctx, self.curves.ptr, n * self.n_hyp * 4).view(np.float32).reshape(n, self.n_hyp) if self.curves else None
+        chips = _slot.download(ctx, self.chips.ptr, n * self.L * self.W * 8).view(np.complex64).reshape(n, self.L, self.W) if self.chips else None
         return rec, curves, chips
 
     def release(self):
@@ -204,11 +197,8 @@ def refocus_slot(ctx, d_slc1, d_slc2, n_az, n_rg, params, range_axis, slot_ptr, 
     outs = _Outputs(ctx, params, max_detections)
     try:
         enqueue(ctx, d_slc1, d_slc2, n_az, n_rg, cp, slot_ptr, max_detections, *outs.ptrs())
-        hdr = _d2h(ctx, slot_ptr, HEADER_BYTES)
-        count, overflow = (int(x) for x in hdr[:8].view("<u4"))
-        if overflow or count > int(max_detections):
-            raise GmtiOverflowError(count, max_detections)
-        rep = _d2h(ctx, slot_ptr + HEADER_BYTES, count * REPORT_DTYPE.itemsize).view(REPORT_DTYPE)
+        count = _slot.raise_if_overflowed(*_slot.header(_slot.fetch_header(ctx, slot_ptr)), max_detections, strict=True)
+        rep = _slot.download(ctx, slot_ptr + HEADER_BYTES, count * REPORT_DTYPE.itemsize).view(REPORT_DTYPE)
         rec, curves, chips = outs.fetch(ctx, count)
     finally:
         outs.release()
@@ -224,11 +214,9 @@ def positions_slot(positions, n_az, n_rg):
         raise ValueError("positions must be an (n, 2) integer array of (i, j)")
     if len(pos) and ((pos[:, 0] < 0).any() or (pos[:, 0] >= n_az).any() or (pos[:, 1] < 0).any() or (pos[:, 1] >= n_rg).any()):
         raise ValueError("a position lies outside the image")
-    raw = np.zeros(HEADER_BYTES + max(len(pos), 1) * REPORT_DTYPE.itemsize, np.uint8)
-    raw[:4].view("<u4")[0] = len(pos)
-    rep = raw[HEADER_BYTES:].view(REPORT_DTYPE)
-    rep["i"][:len(pos)], rep["j"][:len(pos)] = pos[:, 0], pos[:, 1]
-    return raw, pos
+    rep = np.zeros(len(pos), REPORT_DTYPE)
+    rep["i"], rep["j"] = pos[:, 0], pos[:, 1]
+    return _slot.encode(rep, max(len(pos), 1)), pos
 
 
 def gmti_refocus(report_or_positions, slc1, slc2, range_axis, cross_range, *, wavelength_m, platform_speed_mps, prf_hz,

@@ -22,8 +22,9 @@ from typing import Tuple
 
 import numpy as np
 
-from . import _ffi, gmti
+from . import _ffi, slot as _slot
 from ._ffi import SarxError, check
+from .slot import GmtiReport, encode as encode_slot   # noqa: F401
 
 HEADER_BYTES = C.sizeof(_ffi.TrackHeader)
 HEADER_DTYPE = np.dtype([("n_live", "<u4"), ("n_confirmed", "<u4"), ("next_id", "<i4"), ("frames_done", "<u4"), ("births_total", "<u4"),
@@ -92,7 +93,7 @@ class TrackParams:
                                 int(self.max_tracks), int(self.max_detections), 0)
 
     def slot_bytes(self):
-        return gmti.HEADER_BYTES + self.max_detections * gmti.REPORT_DTYPE.itemsize
+        return _slot.slot_bytes(self.max_detections)
 
 
 def table_bytes(cp):
@@ -119,33 +120,6 @@ def enqueue_step(ctx, cp, slot_ptr, frame, table_ptr, assoc_ptr, workspace_ptr):
 def enqueue_run(ctx, cp, stack_ptr, stride, n_frames, table_ptr, assoc_ptr, workspace_ptr):
     """Steps 0 .. n_frames - 1 over slots `stride` bytes apart; only enqueues."""
     check(ctx.lib.sarx_track_run_dev(ctx.h, C.byref(cp), stack_ptr, int(stride), int(n_frames), table_ptr, assoc_ptr, workspace_ptr), ctx.h)
-
-
-def encode_slot(report, max_detections):
-    """A slot's bytes from a GmtiReport, a REPORT_DTYPE array, or a slot's own bytes (padded to the full size)."""
-    size = gmti.HEADER_BYTES + max_detections * gmti.REPORT_DTYPE.itemsize
-    raw = np.zeros(size, np.uint8)
-    if isinstance(report, gmti.GmtiReport):
-        d = report.detections
-        rep = np.zeros(len(d), gmti.REPORT_DTYPE)
-        for k in ("i", "j", "power", "mean", "mag1", "mag2"):
-            rep[k] = d[k]
-        rep["interf_re"], rep["interf_im"] = d["interf"].real, d["interf"].imag
-    else:
-        a = np.asarray(report)
-        if a.dtype == gmti.REPORT_DTYPE:
-            rep = a
-        else:
-            a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-            if a.size > size or a.size < gmti.HEADER_BYTES:
-                raise ValueError("a raw slot is a header and at most max_detections reports")
-            raw[:a.size] = a
-            return raw
-    if len(rep) > max_detections:
-        raise gmti.GmtiOverflowError(len(rep), max_detections)
-    raw[:4].view("<u4")[0] = len(rep)
-    raw[gmti.HEADER_BYTES:gmti.HEADER_BYTES + rep.nbytes] = np.ascontiguousarray(rep).view(np.uint8)
-    return raw
 
 
 class TrackResult:
@@ -197,8 +171,7 @@ def unwrap_speed(v_ati, range_rate, v_amb):
 
 
 def _slot_ij(raw, max_detections):
-    count = min(int(raw[:4].view("<u4")[0]), max_detections)
-    rep = raw[gmti.HEADER_BYTES:gmti.HEADER_BYTES + count * gmti.REPORT_DTYPE.itemsize].view(gmti.REPORT_DTYPE)
+    rep = _slot.reports(raw, min(_slot.header(raw)[0], max_detections))
     return np.stack([rep["i"], rep["j"]], axis=1)
 
 
@@ -220,15 +193,13 @@ class GmtiTracker:
         f = len(self._slots)
         if f >= self.max_frames:
             raise ValueError(f"more than max_frames={self.max_frames} steps")
-        if hasattr(slot, "ptr"):
+        _, stack, on_device = _slot.stage(slot, max_detections=self.params.max_detections, single=True)
+        if on_device:
             ptr = slot.ptr
-            self._slots.append(slot)
         else:
-            raw = encode_slot(slot, self.params.max_detections)
-            buf = self.ctx.to_device(raw)
-            self._own.append(buf)
-            ptr = buf.ptr
-            self._slots.append(raw)
+            self._own.append(self.ctx.to_device(stack[0]))
+            ptr = self._own[-1].ptr
+        self._slots.append(slot if on_device else stack[0])
         enqueue_step(self.ctx, self.cp, ptr, f, self.table.ptr, self.d_assoc.ptr + f * self.params.max_detections * 4, self.ws.ptr)
         return f
 
@@ -240,7 +211,7 @@ class GmtiTracker:
         ij = []
         for s in self._slots:
             if hasattr(s, "ptr"):
-                s = gmti.fetch_slot(self.ctx, s.ptr, md)
+                s = _slot.fetch(self.ctx, s.ptr, md)
             ij.append(_slot_ij(s, md))
         return TrackResult(raw, assoc, ij, frame_dt_s, dr_m, v_ambiguity_mps)
 
@@ -264,13 +235,14 @@ def gmti_track(reports, params=None, *, frame_dt_s, dr_m=None, v_ambiguity_mps=N
         raise ValueError("frame_dt_s must be > 0")
     reports = list(reports)
     if v_ambiguity_mps is None:
-        v_ambiguity_mps = next((r.v_ambiguity_mps for r in reports if isinstance(r, gmti.GmtiReport)), None)
-    md, n = params.max_detections, len(reports)
-    stack = np.zeros((max(n, 1), params.slot_bytes()), np.uint8)
-    for f, r in enumerate(reports):
-        stack[f] = encode_slot(r, md)
+        v_ambiguity_mps = next((r.v_ambiguity_mps for r in reports if isinstance(r, GmtiReport)), None)
+    md, stack, on_device = _slot.stage(reports, max_detections=params.max_detections)
+    if on_device:
+        raise TypeError("gmti_track takes host data; device slots go through GmtiTracker.step")
+    n = len(stack)
     ctx = ctx or default_context()
-    bufs = [ctx.to_device(stack), ctx.alloc(table_bytes(cp)), ctx.alloc(workspace_bytes(cp)), ctx.alloc(max(n, 1) * md * 4)]
+    bufs = [ctx.to_device(stack if n else np.zeros((1, stack.shape[1]), np.uint8)), ctx.alloc(table_bytes(cp)), ctx.alloc(workspace_bytes(cp)),
+            ctx.alloc(max(n, 1) * md * 4)]
     try:
         d_stack, table, ws, d_assoc = bufs
         enqueue_init(ctx, cp, table.ptr)
