@@ -1,4 +1,4 @@
-// What the host units of the C ABI share (api_ctx.hip, api_csa.hip, api_focus.hip, api_comm.hip, api_gmti.hip, api_balance.hip, api_track.hip, api_coherence.hip, api_oscfar.hip, api_cluster.hip, api_atigate.hip): the context behind
+// What the host units of the C ABI share (api_ctx.hip, api_csa.hip, api_focus.hip, api_comm.hip, api_gmti.hip, api_balance.hip, api_track.hip, api_coherence.hip, api_oscfar.hip, api_cluster.hip, api_atigate.hip, api_tdbp_search.hip): the context behind
 // sarx_ctx*, error reporting, the exception guard and the staged host copies.  Host only: no kernel file includes this header.
 #pragma once
 #include "../../include/sarx.h"
@@ -73,8 +73,20 @@ struct sarx_ctx {
     std::string err;
 };
 
+namespace sarx { struct Tdbp; }
+struct sarx_tdbp_plan {                // made and destroyed by api_focus.hip
+    sarx_ctx* ctx = nullptr;
+    sarx::Tdbp* t = nullptr;
+    int n_p = 0, n_s = 0, nx = 0, ny = 0;
+    float2* d_raw = nullptr;           // staging for the host entry points
+    int search_chunks = 0;             // sarx_tdbp_search_set_chunks
+};
+
 namespace sarx {
 
+// the plans alive (api_tdbp_search.hip), so that an entry point can refuse a destroyed one without reading it
+void tdbp_plan_register(const sarx_tdbp_plan* p, bool alive);      // sarx_tdbp_plan_create / _destroy
+bool tdbp_plan_live(const sarx_tdbp_plan* p);
 extern thread_local std::string g_init_error;     // what sarx_last_error(NULL) returns: failures before a context exists (api_ctx.hip)
 int fail(sarx_ctx* c, int code, const char* fmt, ...);
 #define HIPCHK(c, call)                                                                        \

@@ -240,12 +240,7 @@ int sarx_echo_spotlight_dev(sarx_ctx* c, const double* tau_pb, const float* amp_
 }
 
 // ---- time-domain back-projection ---------------------------------------------------------
-struct sarx_tdbp_plan {
-    sarx_ctx* ctx = nullptr;
-    Tdbp* t = nullptr;
-    int n_p = 0, n_s = 0, nx = 0, ny = 0;
-    float2* d_raw = nullptr;       // staging for the host entry point
-};
+// struct sarx_tdbp_plan: api_ctx.h (api_tdbp_search.hip takes plans too, and keeps the list of live ones)
 
 static int sarx_tdbp_plan_create_impl(sarx_ctx* c, int n_pulses, int num_samples, int nx, int ny, const sarx_tdbp_params* k,
                           sarx_tdbp_plan** out) {
@@ -261,6 +256,7 @@ static int sarx_tdbp_plan_create_impl(sarx_ctx* c, int n_pulses, int num_samples
     if (!t) return fail(c, SARX_ERR_UNSUPPORTED, "tdbp plan: %s", err.c_str());
     sarx_tdbp_plan* p = new sarx_tdbp_plan();
     p->ctx = c; p->t = t; p->n_p = n_pulses; p->n_s = num_samples; p->nx = nx; p->ny = ny;
+    tdbp_plan_register(p, true);
     *out = p;
     return SARX_OK;
 }
@@ -270,6 +266,7 @@ int sarx_tdbp_plan_create(sarx_ctx* c, int n_pulses, int num_samples, int nx, in
 }
 int sarx_tdbp_plan_destroy(sarx_tdbp_plan* p) {
     if (!p) return SARX_OK;
+    tdbp_plan_register(p, false);
     hipSetDevice(p->ctx->device);
     sync_all_lanes(p->ctx);
     tdbp_destroy(p->t);

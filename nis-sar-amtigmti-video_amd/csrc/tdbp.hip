@@ -27,16 +27,11 @@
 #include "fft_core.hpp"
 #include "general.h"
 #include "tdbp.h"
+#include "tdbp_search.h"
 
 namespace sarx {
 
 typedef std::complex<double> zd;
-
-struct PulseGeo {            // one 64-byte record per pulse, read with scalar loads
-    double px, py, pz;       // platform position
-    double wx, wy, wz;       // platform velocity - focus velocity  (v_rel, :211)
-    double dt, pad;          // t_pulse - mean(t_pulses) (:203-204); pad = |v_rel|^2
-};
 
 struct TdbpArgs {
     const cf* rc;            // [n_p][n_s] range-compressed pulses
@@ -223,6 +218,7 @@ struct Tdbp {
     double axes_scene = -1.0;     // scene_size the pixel axes on the device were built for
     double2 *part = nullptr, *img = nullptr;
     uint64_t bytes = 0;
+    TdbpSearch* search = nullptr; // scratch of the focus-velocity search (tdbp_search.hip), made by its first call
 };
 
 void tdbp_destroy(Tdbp* t) {
@@ -235,6 +231,7 @@ void tdbp_destroy(Tdbp* t) {
         if (t->geo_done[b]) hipEventDestroy(t->geo_done[b]);
     }
     hipFree(t->part); hipFree(t->img);
+    tdbp_search_free(t->search);
     delete t;
 }
 
@@ -356,8 +353,8 @@ hipError_t tdbp_range_compress(Tdbp* t, const float2* raw, int lo, int hi, hipSt
 // Sample window [lo, hi) that the back-projection can touch: a bound, not an estimate.  Per pulse the pixel rectangle
 // moved by v_f dt is convex, so the transmit range is largest at a corner and smallest at the projection of the
 // platform clamped to the rectangle; |d_rx - d_tx| <= |v_rel| tau_a and |t_shift| <= |v_rel| |k_shift| (:209-219).
-static void sample_window(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double t_start, double scene_size,
-                          int* lo, int* hi) {
+void tdbp_sample_window(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double t_start, double scene_size,
+                        int* lo, int* hi) {
     const double c = t->k.c, fs = t->k.fs, ks = fabs(t->k.fc * 2.0 / t->k.c / t->k.k_rate), h = scene_size / 2;
     double imin = 1e300, imax = -1e300;
     for (const PulseGeo& g : geo) {
@@ -383,7 +380,7 @@ static void sample_window(const Tdbp* t, const std::vector<PulseGeo>& geo, const
 // May the tile kernel stand in for the exact one?  Farthest pixel of a 16 x 16 tile from its reference pixel (index 8 of 16) against
 // the nearest range of any pulse: the first omitted series term of d_tx, 5 u^4 / 128 * d, must stay below 1e-9 m (4e-7 rad of
 // carrier phase at X band).  SARX_TDBP_TILE=0 forces the exact kernel (A/B).
-static bool tdbp_tile_ok(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double scene_size) {
+bool tdbp_tile_ok(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double scene_size) {
     if (const char* ev = getenv("SARX_TDBP_TILE")) if (atoi(ev) == 0) return false;
     if (t->nx < 2 || t->ny < 2) return false;
     const double h = scene_size / 2;
@@ -426,7 +423,7 @@ hipError_t tdbp_focus(Tdbp* t, const float2* raw, const double* pos, const doubl
         g.dt = t_pulses[p] - mean; g.pad = g.wx * g.wx + g.wy * g.wy + g.wz * g.wz;
     }
     int lo = 0, hi = t->n_s;
-    if (!all_samples && !t->full_rc) sample_window(t, geo, vel_focus, t_start, scene_size, &lo, &hi);
+    if (!all_samples && !t->full_rc) tdbp_sample_window(t, geo, vel_focus, t_start, scene_size, &lo, &hi);
     TCK(tdbp_range_compress(t, raw, lo, hi, st));
     memcpy(t->h_geo[slot], geo.data(), geo.size() * sizeof(PulseGeo));
     TCK(hipMemcpyAsync(t->geo[slot], t->h_geo[slot], geo.size() * sizeof(PulseGeo), hipMemcpyHostToDevice, st));
@@ -455,6 +452,26 @@ hipError_t tdbp_focus(Tdbp* t, const float2* raw, const double* pos, const doubl
     TCK(hipGetLastError());
     return hipEventRecord(t->geo_done[slot], st);
 }
+
+// ---- the plan's internals for the focus-velocity search (tdbp_search.hip) ----
+hipError_t tdbp_ensure_axes(Tdbp* t, double scene_size, hipStream_t st) {     // as tdbp_focus keeps them: once per scene size
+    if (t->axes_scene == scene_size) return hipSuccess;
+    std::vector<double> xa, ya;
+    linspace(-scene_size / 2, scene_size / 2, t->nx, xa);
+    linspace(-scene_size / 2, scene_size / 2, t->ny, ya);
+    TCK(hipStreamSynchronize(st));
+    TCK(hipMemcpy(t->xax, xa.data(), xa.size() * sizeof(double), hipMemcpyHostToDevice));
+    TCK(hipMemcpy(t->yax, ya.data(), ya.size() * sizeof(double), hipMemcpyHostToDevice));
+    t->axes_scene = scene_size;
+    return hipSuccess;
+}
+TdbpView tdbp_view(const Tdbp* t) {
+    TdbpView v{};
+    v.n_p = t->n_p; v.n_s = t->n_s; v.nx = t->nx; v.ny = t->ny; v.k = t->k;
+    v.rc = t->rc; v.xax = t->xax; v.yax = t->yax; v.full_rc = t->full_rc;
+    return v;
+}
+TdbpSearch*& tdbp_search_slot(Tdbp* t) { return t->search; }
 
 const double2* tdbp_image(const Tdbp* t) { return t->img; }
 const float2* tdbp_rc(const Tdbp* t) { return t->rc; }

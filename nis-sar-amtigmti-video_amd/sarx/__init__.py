@@ -17,6 +17,7 @@ from .coherence import CoherenceParams, CoherenceResult, coherence, coherence_st
 from .track import GmtiTracker, TrackOverflowError, TrackParams, TrackResult, gmti_track
 from .cluster import ClusterParams, GmtiPlots, gmti_cluster
 from .atigate import AtiGateParams, gmti_ati_gate
+from .tdbp_search import TdbpSearchResult, tdbp_autofocus, tdbp_search, tdbp_velocity_line
 from .focus import (FocusFuture, ati_dpca, clear_plan_cache, dpca_pulse_shift, focus_ati_dpca, focus_stream, phase_balance,
                     sar_focus_csa, sar_focus_csa_async, two_channel_workspace)
 
@@ -27,4 +28,5 @@ __all__ = ["SarxError", "Context", "CsaPlan", "FocusLanes", "add_noise_rel_dev",
            "GmtiOverflowError", "gmti_refocus", "RefocusParams", "RefocusResult", "channel_balance", "BalanceParams", "ChannelBalance",
            "coherence", "coherence_stack", "CoherenceParams", "CoherenceResult",
            "gmti_track", "GmtiTracker", "TrackParams", "TrackResult", "TrackOverflowError",
-           "gmti_cluster", "ClusterParams", "GmtiPlots", "gmti_ati_gate", "AtiGateParams"]
+           "gmti_cluster", "ClusterParams", "GmtiPlots", "gmti_ati_gate", "AtiGateParams",
+           "tdbp_search", "tdbp_velocity_line", "tdbp_autofocus", "TdbpSearchResult"]

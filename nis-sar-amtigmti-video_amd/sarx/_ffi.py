@@ -336,6 +336,23 @@ ATIGATE_SIGNATURES = {
     "sarx_atigate_step_dev": (_i, [_vp, _P(AtiGateParams), _vp, _vp, _i, _i, _vp, _vp, _vp]),
 }
 
+# include/sarx_tdbp_search.h: the back-projection's focus-velocity search, a tenth table bound the same way
+TDBP_SEARCH_MAX_HYP, TDBP_SEARCH_MAX_CHUNKS = 1024, 64                        # SARX_TDBP_SEARCH_MAX_HYP, _MAX_CHUNKS
+
+
+class TdbpSearchRecord(C.Structure):
+    """sarx_tdbp_search_record (32 bytes)"""
+    _fields_ = [("s2", C.c_double), ("s4", C.c_double), ("peak", C.c_double), ("peak_ix", C.c_int32), ("peak_iy", C.c_int32)]
+
+
+TDBP_SEARCH_SIGNATURES = {
+    "sarx_tdbp_search_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _i, _d, _vp, _vp]),
+    "sarx_tdbp_search_host": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _i, _d, _vp, _vp]),
+    "sarx_tdbp_search_route": (_i, [_vp, _P(_i)]),
+    "sarx_tdbp_search_set_chunks": (_i, [_vp, _i]),
+    "sarx_tdbp_search_metric_dev": (_i, [_vp, _vp, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -350,7 +367,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
             list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()) + \
-            list(CLUSTER_SIGNATURES.items()) + list(ATIGATE_SIGNATURES.items()):
+            list(CLUSTER_SIGNATURES.items()) + list(ATIGATE_SIGNATURES.items()) + list(TDBP_SEARCH_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -131,6 +131,7 @@ class TdbpPlan:
         check(ctx.lib.sarx_tdbp_plan_create(ctx.h, *self.shape, C.byref(prm), C.byref(self.h)), ctx.h)
         ctx._plans.add(self)          # closed with the context, before sarx_destroy
         self._d_img = None            # the device image of the device-in path, kept across frames (a frame loop allocated and freed it per frame)
+        self._d_search = {}           # tdbp_search's device records / image stack of the device-in path, kept across calls
 
     def focus(self, raw, pos_plat, vel_plat, t_start, vel_focus, t_pulses, scene_size, want_rc=False, d_image=None):
         n_p, n_s, nx, ny = self.shape
@@ -174,7 +175,10 @@ class TdbpPlan:
             self.ctx.lib.sarx_tdbp_plan_destroy(self.h)
             if self._d_img is not None:
                 self._d_img.release()
+            for b in self._d_search.values():
+                b.release()
         self._d_img = None
+        self._d_search = {}
         self.h = None
 
     def __del__(self):
@@ -196,7 +200,12 @@ def tdbp_gpu(raw_t, pos_plat, vel_plat, t_start, num_samples, vel_focus, t_pulse
     its own plan, i.e. its own scratch)."""
     k = consts or batch_constants()
     ctx = ctx or default_context()
-    n_p = len(t_pulses)
+    plan = cached_plan(ctx, k, len(t_pulses), num_samples, nx, ny)
+    return plan.focus(raw_t, pos_plat, vel_plat, t_start, vel_focus, t_pulses, scene_size, d_image=d_image)
+
+
+def cached_plan(ctx, k, n_p, num_samples, nx, ny):
+    """The plan tdbp_gpu keeps for this context, lane, shape and waveform (tdbp_search shares it: one scratch, one compression)."""
     key = (id(ctx), getattr(ctx, "_lane", 0), n_p, int(num_samples), int(nx), int(ny), k["C"], k["FC"], k["FS"], k["T_P"], k["K_RATE"])
     plan = _plans.get(key)
     if plan is None or plan.h is None:         # closed together with its Context: never reuse a dead handle
@@ -204,4 +213,4 @@ def tdbp_gpu(raw_t, pos_plat, vel_plat, t_start, num_samples, vel_focus, t_pulse
         if len(_plans) >= 8:
             _plans.pop(next(iter(_plans))).close()
         plan = _plans[key] = TdbpPlan(ctx, n_p, num_samples, nx, ny, k)
-    return plan.focus(raw_t, pos_plat, vel_plat, t_start, vel_focus, t_pulses, scene_size, d_image=d_image)
+    return plan
