@@ -1,0 +1,114 @@
+// One pixel and pulse of the time-domain back-projection (sar_batch_sim.py:205-232), stated once for the focus kernels of tdbp.hip
+// and the focus-velocity search kernels of tdbp_search.hip.  A kernel keeps only its tile and pixel coordinates, where the focus
+// velocity v_f and w = v_plat - v_f come from, the batch loop of the tile form and the place of its partial image.
+// Every statement groups its operands as the reference parity (1e-4) was measured with: -ffp-contract=on fuses inside a statement
+// only, so splitting or merging one changes bits.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "fft_core.hpp"
+
+namespace sarx {
+
+// A: the kernel's argument struct (TdbpArgs, SearchArgs); read here: rc [n_p][n_s], n_s, half_w, inv_c, fc, fs, t_start, k_shift,
+// inv_ns - the fields tdbp_fill_args (tdbp_plan.h) sets.
+
+// the compressed pulse p at the normalised coordinate xn, as F.grid_sample reads it, times the carrier phase; summed in fp64
+template <class A> __device__ __forceinline__ void tdbp_sample(const A& c, float xn, double tau, int p, double& acc_re, double& acc_im) {
+    const float x = __fmaf_rn(xn + 1.0f, c.half_w, -0.5f);                                  // grid_sample unnormalise
+    const float x0 = floorf(x);
+    const float w = x - x0, e = 1.0f - w;
+    const int i0 = (int)x0;
+    const cf* row = c.rc + (size_t)p * c.n_s;
+    cf v0 = make_float2(0.f, 0.f), v1 = v0;
+    if (i0 >= 0 && i0 < c.n_s) v0 = row[i0];
+    if (i0 + 1 >= 0 && i0 + 1 < c.n_s) v1 = row[i0 + 1];
+    const float s_re = fmaf(v1.x, w, v0.x * e), s_im = fmaf(v1.y, w, v0.y * e);
+    const cf ph = cis_rev(c.fc * tau);                                                      // :231-232
+    acc_re += (double)(s_re * ph.x - s_im * ph.y);
+    acc_im += (double)(s_re * ph.y + s_im * ph.x);
+}
+
+// The exact form.  d: from the transmitter to the pixel moved with the focus velocity (:205-208); w = v_rel (:211), w2 = |w|^2.
+template <class A> __device__ __forceinline__ void tdbp_exact_pixel(const A& c, double dx, double dy, double dz, double wx, double wy,
+                                                                   double wz, double w2, int p, double& acc_re, double& acc_im) {
+    const double s_tx = fma(dx, dx, fma(dy, dy, dz * dz));
+    const double inv_d = rsqrt(s_tx);                                                       // one reciprocal square root
+    const double d_tx = s_tx * inv_d;                                                       // serves range and unit vector
+    const double dw = wx * dx + wy * dy + wz * dz;
+    const double v_rad = dw * inv_d;                                                        // :210-212
+    const double t_shift = v_rad * c.k_shift;                                               // :213
+    const double tau_a = 2.0 * d_tx * c.inv_c;                                              // :215
+    // (g + v_f tau_a) - (pos + vel tau_a) = d - v_rel tau_a (:216-218), so
+    // d_rx^2 = d_tx^2 (1 - e), e = tau_a (2 d.w - tau_a |w|^2) / d_tx^2 ~ 1e-4: sqrt(1 - e) by its series
+    // (e^5 / d_tx < 1e-20 relative; a second fp64 square root costs three times as much)
+    const double eps = tau_a * (2.0 * dw - tau_a * w2) * (inv_d * inv_d);
+    const double sq = fma(eps, fma(eps, fma(eps, fma(eps, -5.0 / 128.0, -1.0 / 16.0), -1.0 / 8.0), -0.5), 1.0);
+    const double d_rx = d_tx * sq;
+    const double tau = (d_tx + d_rx) * c.inv_c;                                             // :219
+    const double idx_f = (tau - c.t_start + t_shift) * c.fs;                                // :221
+    const float xn = (float)(2.0 * (idx_f * c.inv_ns) - 1.0);                               // :222, .float() :226
+    tdbp_sample(c, xn, tau, p, acc_re, acc_im);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The same sum with the geometry expanded about the tile's reference pixel (round 5).  A 16 x 16 tile spans ~10 m at
+// ranges of hundreds of kilometres, so per (tile, pulse) everything that needs a square root or a division is computed
+// ONCE - by one lane per pulse, 256 pulses per batch, handed to the tile through LDS - and a pixel keeps only
+//   d_tx = d0 sqrt(1 + u),  u = (2 D.q + |q|^2) / d0^2        as d0 (1 + u/2 - u^2/8 + u^3/16)   (u <= 5e-5: next term 5 u^4 / 128)
+//   d_tx - d_rx = E0 + grad E . q                             (E = d_tx (1 - sqrt(1 + 4|w|^2/c^2 - 4 r / c)), r = d.w / d_tx: its
+//                                                              leading term (2/c) d.w is exactly linear in q, the rest < 1e-11 m)
+//   t_shift fs = ts0 + grad ts . q                            (fp32: it only moves the interpolation coordinate, by < 1e-6 sample)
+// with q the pixel's offset from the reference pixel (exact differences of the axis tables).  22 fp64 instructions per
+// pixel and pulse instead of 48; the launcher takes this form only when 5 u_max^4 / 128 * d_max < 1e-9 m over all
+// pulses (tdbp_tile_ok), otherwise the exact one above.  Same pulse order per pixel and the same fp64 accumulation.
+// ------------------------------------------------------------------------------------------------------------
+struct __attribute__((aligned(16))) TilePulse {
+    double a1, a2;           // 2 Dx, 2 Dy
+    double inv_d0sq, d0;
+    double e0, ex;
+    double ey; float ts0, tsx;
+    float tsy, pad0; double pad1;
+};
+static_assert(sizeof(TilePulse) == 80, "five 16-byte LDS reads per pulse");
+static constexpr int TP_BATCH = 256;
+
+// the record of one pulse: d and w as in the exact form, taken at the tile's reference pixel
+template <class A> __device__ __forceinline__ TilePulse tdbp_tile_prologue(const A& c, double dx, double dy, double dz, double wx,
+                                                                          double wy, double wz, double w2) {
+    const double s0 = fma(dx, dx, fma(dy, dy, dz * dz));
+    const double inv_d = rsqrt(s0), d0 = s0 * inv_d;
+    const double dw = wx * dx + wy * dy + wz * dz;
+    const double r = dw * inv_d;                                                            // :210-212
+    const double tau_a = 2.0 * d0 * c.inv_c;
+    const double eps = tau_a * (2.0 * dw - tau_a * w2) * (inv_d * inv_d);
+    const double sm1 = eps * fma(eps, fma(eps, fma(eps, -5.0 / 128.0, -1.0 / 16.0), -1.0 / 8.0), -0.5);   // sqrt(1 - eps) - 1
+    const double ux = dx * inv_d, uy = dy * inv_d;                                          // unit vector, ground components
+    const double f = -sm1, fp = 2.0 * c.inv_c / (1.0 + sm1);                                // F(r) and F'(r)
+    const double rx = (wx - r * ux) * inv_d, ry = (wy - r * uy) * inv_d;                    // grad r
+    TilePulse t;
+    t.a1 = 2.0 * dx; t.a2 = 2.0 * dy; t.inv_d0sq = inv_d * inv_d; t.d0 = d0;
+    t.e0 = d0 * f;
+    t.ex = fma(d0 * fp, rx, f * ux); t.ey = fma(d0 * fp, ry, f * uy);
+    const double ks = c.k_shift * c.fs;
+    t.ts0 = (float)(r * ks); t.tsx = (float)(rx * ks); t.tsy = (float)(ry * ks);
+    t.pad0 = 0.f; t.pad1 = 0.0;
+    return t;
+}
+
+// q: the pixel's offset from the reference pixel, q2 = |q|^2, qxf, qyf = (float)q; two_inv_ns = 2 / n_s
+template <class A> __device__ __forceinline__ void tdbp_tile_pixel(const A& c, const TilePulse& t, double qx, double qy, double q2,
+                                                                  float qxf, float qyf, double two_inv_ns, int p, double& acc_re,
+                                                                  double& acc_im) {
+    const double u = fma(t.a1, qx, fma(t.a2, qy, q2)) * t.inv_d0sq;
+    const double h = u * fma(u, fma(u, 1.0 / 16.0, -1.0 / 8.0), 0.5);
+    const double d_tx = fma(t.d0, h, t.d0);
+    const double e = fma(t.ex, qx, fma(t.ey, qy, t.e0));                                    // d_tx - d_rx
+    const double tau = fma(2.0, d_tx, -e) * c.inv_c;                                        // :219
+    const float ts = fmaf(t.tsx, qxf, fmaf(t.tsy, qyf, t.ts0));                             // t_shift * fs (:213)
+    const double idx_f = fma(tau - c.t_start, c.fs, (double)ts);                            // :221
+    const float xn = (float)fma(idx_f, two_inv_ns, -1.0);                                   // :222, .float() :226
+    tdbp_sample(c, xn, tau, p, acc_re, acc_im);
+}
+
+}  // namespace sarx

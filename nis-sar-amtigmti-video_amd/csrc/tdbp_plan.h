@@ -1,0 +1,58 @@
+// The back-projection plan itself: what tdbp.hip and the focus-velocity search (tdbp_search.hip) share and no other unit sees.
+#pragma once
+#include <map>
+#include <vector>
+
+#include "tdbp_pixel.hpp"
+#include "tdbp_search.h"
+
+namespace sarx {
+
+struct PulseGeo {            // one 64-byte record per pulse, read with scalar loads
+    double px, py, pz;       // platform position
+    double wx, wy, wz;       // platform velocity - focus velocity  (v_rel, :211)
+    double dt, pad;          // t_pulse - mean(t_pulses) (:203-204); pad = |v_rel|^2
+};
+
+struct Tdbp {
+    int n_p = 0, n_s = 0, nx = 0, ny = 0, taps = 0, m = 0, blk = 0, chunks = 1, per_chunk = 0;
+    sarx_tdbp_params k{};
+    const cf* tw_all = nullptr;
+    cf *work = nullptr, *rc = nullptr;   // rc: [n_p][n_s], filled by tdbp_range_compress
+    std::map<int, cf*> hhat;      // conj spectrum of the reference chirp per FFT length (device order)
+    int l_ref = 0;
+    bool full_rc = false;         // SARX_TDBP_FULL_RC=1: always compress every sample
+    bool three_launch = false;    // SARX_TDBP_RC_FUSED=0: copy-in, two transforms, copy-out per block (the form of rounds 2-4, for A/B)
+    int win_lo = 0, win_hi = 0;   // samples compressed by the last call
+    // per-pulse table, double-buffered: frame i + 1's table is staged in page-locked memory and copied on the stream while frame i
+    // still reads its own - no stream synchronisation per frame (the copy of rounds 2-4 was a blocking one behind a hipStreamSynchronize
+    // that made the host wait for the frame's echo, noise and range compression before it could enqueue the back-projection)
+    PulseGeo* geo[2] = {nullptr, nullptr};
+    PulseGeo* h_geo[2] = {nullptr, nullptr};
+    hipEvent_t geo_done[2] = {nullptr, nullptr};
+    int geo_slot = 0;
+    double *xax = nullptr, *yax = nullptr;   // pixel axes, valid after tdbp_ensure_axes
+    double axes_scene = -1.0;     // scene_size the pixel axes on the device were built for
+    double2 *part = nullptr, *img = nullptr;
+    uint64_t bytes = 0;
+    TdbpSearch* search = nullptr; // scratch of the focus-velocity search (tdbp_search.hip), made by its first call, freed by tdbp_destroy
+};
+
+hipError_t tdbp_range_compress(Tdbp* t, const float2* raw, int lo, int hi, hipStream_t st);
+hipError_t tdbp_ensure_axes(Tdbp* t, double scene_size, hipStream_t st);
+// position and dt = t_pulse - mean(t_pulses) of every pulse; then w = v_plat - vf and |w|^2 for one focus velocity
+void tdbp_pulse_table(const Tdbp* t, const double* pos, const double* t_pulses, std::vector<PulseGeo>& geo);
+void tdbp_set_focus(std::vector<PulseGeo>& geo, const double* vel, const double* vf);
+// geo holds w = v_plat - vf for the SAME vf
+void tdbp_sample_window(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double t_start, double scene_size,
+                        int* lo, int* hi);
+bool tdbp_tile_ok(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double scene_size);
+// the kernel arguments that the focus launch (TdbpArgs) and the search launch (SearchArgs) share
+template <class A> void tdbp_fill_args(const Tdbp* t, double t_start, int per_chunk, A& a) {
+    a.rc = t->rc; a.xax = t->xax; a.yax = t->yax;
+    a.inv_c = 1.0 / t->k.c; a.fc = t->k.fc; a.fs = t->k.fs; a.t_start = t_start;
+    a.k_shift = -t->k.fc * 2.0 / t->k.c / t->k.k_rate;
+    a.inv_ns = 1.0 / (double)t->n_s; a.half_w = (float)t->n_s / 2.0f;
+    a.n_p = t->n_p; a.n_s = t->n_s; a.nx = t->nx; a.ny = t->ny; a.per_chunk = per_chunk;
+}
+}  // namespace sarx

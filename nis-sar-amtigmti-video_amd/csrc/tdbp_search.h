@@ -6,6 +6,7 @@
 #include "tdbp.h"
 
 namespace sarx {
+struct TdbpSearch;                                      // the search's scratch, owned by the plan
 // raw: device [n_p][n_s]; pos, vel: host [n_p][3]; t_pulses: host [n_p]; vel_hyps: host [n_hyp][3] (finite, 1 <= n_hyp <= MAX_HYP: the
 // caller checked).  d_images: device complex128 [n_hyp][ny][nx] or NULL; d_records: device [n_hyp].  chunks: pulse chunks, 0 = chosen here.
 hipError_t tdbp_search(Tdbp* t, const float2* raw, const double* pos, const double* vel, const double* t_pulses, double t_start,

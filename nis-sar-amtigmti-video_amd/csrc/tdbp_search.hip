@@ -7,7 +7,8 @@
 //     table holds the platform state alone (position, velocity, dt), uploaded once; w = v_plat - v_h and |w|^2 are formed per
 //     hypothesis from a device table [n_hyp][3] - per pixel and pulse in the exact form, in the per-(tile, pulse) prologue lane in
 //     the tile form, where they cost nothing per pixel.  Everything else - the arithmetic, the float32 interpolation coordinate,
-//     the pulse order per pixel, the fp64 accumulation - is that of the focus kernels.  Partial images [n_hyp][chunks][ny*nx].
+//     the fp64 accumulation - is the code the focus kernels run (tdbp_pixel.hpp), in the same pulse order per pixel.  Partial
+//     images [n_hyp][chunks][ny*nx].
 //   3 metric launch: one 1024-thread workgroup per hypothesis sums the chunks of every pixel in chunk order, writes the image
 //     when a stack is asked for, and folds P = re^2 + im^2 (products and sum rounded one by one, so P is what fp64 NumPy gives)
 //     into s2 = sum P, s4 = sum P^2, the peak and its place: thread t takes pixels t, t + 1024, ... in rising order, then a
@@ -18,8 +19,7 @@
 #include <cstring>
 #include <vector>
 
-#include "fft_core.hpp"
-#include "tdbp_search.h"
+#include "tdbp_plan.h"
 
 namespace sarx {
 
@@ -58,49 +58,15 @@ __global__ __launch_bounds__(256) void tdbp_search_kernel(SearchArgs a) {
         const double dx = fma(vfx, g.dt, gx0) - g.px;
         const double dy = fma(vfy, g.dt, gy0) - g.py;
         const double dz = vfz * g.dt - g.pz;
-        const double s_tx = fma(dx, dx, fma(dy, dy, dz * dz));
-        const double inv_d = rsqrt(s_tx);
-        const double d_tx = s_tx * inv_d;
-        const double dw = wx * dx + wy * dy + wz * dz;
-        const double v_rad = dw * inv_d;
-        const double t_shift = v_rad * a.k_shift;
-        const double tau_a = 2.0 * d_tx * a.inv_c;
-        const double eps = tau_a * (2.0 * dw - tau_a * w2) * (inv_d * inv_d);
-        const double sq = fma(eps, fma(eps, fma(eps, fma(eps, -5.0 / 128.0, -1.0 / 16.0), -1.0 / 8.0), -0.5), 1.0);
-        const double d_rx = d_tx * sq;
-        const double tau = (d_tx + d_rx) * a.inv_c;
-        const double idx_f = (tau - a.t_start + t_shift) * a.fs;
-        const float xn = (float)(2.0 * (idx_f * a.inv_ns) - 1.0);
-        const float x = __fmaf_rn(xn + 1.0f, a.half_w, -0.5f);
-        const float x0 = floorf(x);
-        const float w = x - x0, e = 1.0f - w;
-        const int i0 = (int)x0;
-        const cf* row = a.rc + (size_t)p * a.n_s;
-        cf v0 = make_float2(0.f, 0.f), v1 = v0;
-        if (i0 >= 0 && i0 < a.n_s) v0 = row[i0];
-        if (i0 + 1 >= 0 && i0 + 1 < a.n_s) v1 = row[i0 + 1];
-        const float s_re = fmaf(v1.x, w, v0.x * e), s_im = fmaf(v1.y, w, v0.y * e);
-        const cf ph = cis_rev(a.fc * tau);
-        acc_re += (double)(s_re * ph.x - s_im * ph.y);
-        acc_im += (double)(s_re * ph.y + s_im * ph.x);
+        tdbp_exact_pixel(a, dx, dy, dz, wx, wy, wz, w2, p, acc_re, acc_im);
     }
     const size_t n_pix = (size_t)a.nx * a.ny;
     if (live) a.part[((size_t)blockIdx.z * a.chunks + blockIdx.y) * n_pix + (size_t)iy * a.nx + ix] = make_double2(acc_re, acc_im);
 }
 
-// tdbp_tile_kernel's record and batch (tdbp.hip): the prologue lane forms w of this hypothesis, the pixel loop is unchanged
-struct __attribute__((aligned(16))) SearchTilePulse {
-    double a1, a2;
-    double inv_d0sq, d0;
-    double e0, ex;
-    double ey; float ts0, tsx;
-    float tsy, pad0; double pad1;
-};
-static_assert(sizeof(SearchTilePulse) == 80, "five 16-byte LDS reads per pulse");
-static constexpr int STP_BATCH = 256;
-
+// tdbp_tile_kernel with the prologue lane forming w of this hypothesis
 __global__ __launch_bounds__(256) void tdbp_search_tile_kernel(SearchArgs a) {
-    __shared__ SearchTilePulse s_tp[STP_BATCH];
+    __shared__ TilePulse s_tp[TP_BATCH];
     const int tiles_x = (a.nx + 15) >> 4;
     const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
     const int ix = tx * 16 + (threadIdx.x & 15), iy = ty * 16 + (threadIdx.x >> 4);
@@ -113,57 +79,18 @@ __global__ __launch_bounds__(256) void tdbp_search_tile_kernel(SearchArgs a) {
     const int p0 = blockIdx.y * a.per_chunk, p1 = min(a.n_p, p0 + a.per_chunk);
     const double two_inv_ns = 2.0 * a.inv_ns;
     double acc_re = 0.0, acc_im = 0.0;
-    for (int pb = p0; pb < p1; pb += STP_BATCH) {
-        const int nb = min(STP_BATCH, p1 - pb);
+    for (int pb = p0; pb < p1; pb += TP_BATCH) {
+        const int nb = min(TP_BATCH, p1 - pb);
         __syncthreads();                                   // the previous batch has been consumed
         if ((int)threadIdx.x < nb) {
             const SearchGeo g = a.geo[pb + threadIdx.x];
             const double wx = g.vx - vfx, wy = g.vy - vfy, wz = g.vz - vfz;
             const double w2 = wx * wx + wy * wy + wz * wz;
             const double dx = fma(vfx, g.dt, xc) - g.px, dy = fma(vfy, g.dt, yc) - g.py, dz = vfz * g.dt - g.pz;
-            const double s0 = fma(dx, dx, fma(dy, dy, dz * dz));
-            const double inv_d = rsqrt(s0), d0 = s0 * inv_d;
-            const double dw = wx * dx + wy * dy + wz * dz;
-            const double r = dw * inv_d;
-            const double tau_a = 2.0 * d0 * a.inv_c;
-            const double eps = tau_a * (2.0 * dw - tau_a * w2) * (inv_d * inv_d);
-            const double sm1 = eps * fma(eps, fma(eps, fma(eps, -5.0 / 128.0, -1.0 / 16.0), -1.0 / 8.0), -0.5);
-            const double ux = dx * inv_d, uy = dy * inv_d;
-            const double f = -sm1, fp = 2.0 * a.inv_c / (1.0 + sm1);
-            const double rx = (wx - r * ux) * inv_d, ry = (wy - r * uy) * inv_d;
-            SearchTilePulse t;
-            t.a1 = 2.0 * dx; t.a2 = 2.0 * dy; t.inv_d0sq = inv_d * inv_d; t.d0 = d0;
-            t.e0 = d0 * f;
-            t.ex = fma(d0 * fp, rx, f * ux); t.ey = fma(d0 * fp, ry, f * uy);
-            const double ks = a.k_shift * a.fs;
-            t.ts0 = (float)(r * ks); t.tsx = (float)(rx * ks); t.tsy = (float)(ry * ks);
-            t.pad0 = 0.f; t.pad1 = 0.0;
-            s_tp[threadIdx.x] = t;
+            s_tp[threadIdx.x] = tdbp_tile_prologue(a, dx, dy, dz, wx, wy, wz, w2);
         }
         __syncthreads();
-        for (int k = 0; k < nb; ++k) {
-            const SearchTilePulse& t = s_tp[k];
-            const double u = fma(t.a1, qx, fma(t.a2, qy, q2)) * t.inv_d0sq;
-            const double h = u * fma(u, fma(u, 1.0 / 16.0, -1.0 / 8.0), 0.5);
-            const double d_tx = fma(t.d0, h, t.d0);
-            const double e = fma(t.ex, qx, fma(t.ey, qy, t.e0));
-            const double tau = fma(2.0, d_tx, -e) * a.inv_c;
-            const float ts = fmaf(t.tsx, qxf, fmaf(t.tsy, qyf, t.ts0));
-            const double idx_f = fma(tau - a.t_start, a.fs, (double)ts);
-            const float xn = (float)fma(idx_f, two_inv_ns, -1.0);
-            const float x = __fmaf_rn(xn + 1.0f, a.half_w, -0.5f);
-            const float x0 = floorf(x);
-            const float w = x - x0, ew = 1.0f - w;
-            const int i0 = (int)x0;
-            const cf* row = a.rc + (size_t)(pb + k) * a.n_s;
-            cf v0 = make_float2(0.f, 0.f), v1 = v0;
-            if (i0 >= 0 && i0 < a.n_s) v0 = row[i0];
-            if (i0 + 1 >= 0 && i0 + 1 < a.n_s) v1 = row[i0 + 1];
-            const float s_re = fmaf(v1.x, w, v0.x * ew), s_im = fmaf(v1.y, w, v0.y * ew);
-            const cf ph = cis_rev(a.fc * tau);
-            acc_re += (double)(s_re * ph.x - s_im * ph.y);
-            acc_im += (double)(s_re * ph.y + s_im * ph.x);
-        }
+        for (int k = 0; k < nb; ++k) tdbp_tile_pixel(a, s_tp[k], qx, qy, q2, qxf, qyf, two_inv_ns, pb + k, acc_re, acc_im);
     }
     const size_t n_pix = (size_t)a.nx * a.ny;
     if (live) a.part[((size_t)blockIdx.z * a.chunks + blockIdx.y) * n_pix + (size_t)iy * a.nx + ix] = make_double2(acc_re, acc_im);
@@ -245,19 +172,17 @@ void tdbp_search_free(TdbpSearch* s) {
 #define SCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 static hipError_t search_scratch(Tdbp* t, TdbpSearch** out) {
-    TdbpSearch*& slot = tdbp_search_slot(t);
-    if (!slot) {
-        const TdbpView v = tdbp_view(t);
+    if (!t->search) {
         TdbpSearch* s = new TdbpSearch();
-        hipError_t e = hipMalloc(&s->geo, (size_t)v.n_p * sizeof(SearchGeo));
-        if (e == hipSuccess) e = hipHostMalloc(&s->h_geo, (size_t)v.n_p * sizeof(SearchGeo), hipHostMallocDefault);
+        hipError_t e = hipMalloc(&s->geo, (size_t)t->n_p * sizeof(SearchGeo));
+        if (e == hipSuccess) e = hipHostMalloc(&s->h_geo, (size_t)t->n_p * sizeof(SearchGeo), hipHostMallocDefault);
         if (e == hipSuccess) e = hipMalloc(&s->hyps, (size_t)SARX_TDBP_SEARCH_MAX_HYP * 3 * sizeof(double));
         if (e == hipSuccess) e = hipHostMalloc(&s->h_hyps, (size_t)SARX_TDBP_SEARCH_MAX_HYP * 3 * sizeof(double), hipHostMallocDefault);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s->up_done, hipEventDisableTiming);
         if (e != hipSuccess) { tdbp_search_free(s); return e; }
-        slot = s;
+        t->search = s;
     }
-    *out = slot;
+    *out = t->search;
     return hipSuccess;
 }
 
@@ -270,9 +195,9 @@ static hipError_t grow(double2** buf, size_t* cap, size_t need) {
     return hipSuccess;
 }
 
-static hipError_t launch_metric(const TdbpView& v, const double2* part, int chunks, int n_hyp, double2* d_images,
+static hipError_t launch_metric(const Tdbp* t, const double2* part, int chunks, int n_hyp, double2* d_images,
                                 sarx_tdbp_search_record* d_records, hipStream_t st) {
-    hipLaunchKernelGGL(tdbp_search_metric_kernel, dim3(n_hyp), dim3(MT), 0, st, part, chunks, (size_t)v.nx * v.ny, v.nx, d_images, d_records);
+    hipLaunchKernelGGL(tdbp_search_metric_kernel, dim3(n_hyp), dim3(MT), 0, st, part, chunks, (size_t)t->nx * t->ny, t->nx, d_images, d_records);
     return hipGetLastError();
 }
 
@@ -281,29 +206,17 @@ hipError_t tdbp_search(Tdbp* t, const float2* raw, const double* pos, const doub
                        sarx_tdbp_search_record* d_records, hipStream_t st) {
     TdbpSearch* s = nullptr;
     SCK(search_scratch(t, &s));
-    const TdbpView v = tdbp_view(t);
-    const int n_p = v.n_p;
-    double mean = 0.0;
-    for (int p = 0; p < n_p; ++p) mean += t_pulses[p];
-    mean /= (double)n_p;
+    const int n_p = t->n_p;
     // window and route: the bound and the tile condition of the focus, evaluated for every hypothesis
-    std::vector<PulseGeo> geo(n_p);
-    for (int p = 0; p < n_p; ++p) {
-        PulseGeo& g = geo[p];
-        g.px = pos[3 * p]; g.py = pos[3 * p + 1]; g.pz = pos[3 * p + 2];
-        g.dt = t_pulses[p] - mean;
-    }
-    int lo = v.n_s, hi = 0;
+    std::vector<PulseGeo> geo;
+    tdbp_pulse_table(t, pos, t_pulses, geo);
+    int lo = t->n_s, hi = 0;
     bool tile = true;
     for (int h = 0; h < n_hyp; ++h) {
         const double* vf = vel_hyps + 3 * h;
-        for (int p = 0; p < n_p; ++p) {
-            PulseGeo& g = geo[p];
-            g.wx = vel[3 * p] - vf[0]; g.wy = vel[3 * p + 1] - vf[1]; g.wz = vel[3 * p + 2] - vf[2];
-            g.pad = g.wx * g.wx + g.wy * g.wy + g.wz * g.wz;
-        }
-        int l = 0, u = v.n_s;
-        if (!v.full_rc) tdbp_sample_window(t, geo, vf, t_start, scene_size, &l, &u);
+        tdbp_set_focus(geo, vel, vf);
+        int l = 0, u = t->n_s;
+        if (!t->full_rc) tdbp_sample_window(t, geo, vf, t_start, scene_size, &l, &u);
         if (u > l) { if (l < lo) lo = l; if (u > hi) hi = u; }
         if (tile) tile = tdbp_tile_ok(t, geo, vf, scene_size);
     }
@@ -311,9 +224,9 @@ hipError_t tdbp_search(Tdbp* t, const float2* raw, const double* pos, const doub
     SCK(hipEventSynchronize(s->up_done));                  // the previous call's uploads have left the staging (at once as a rule)
     for (int p = 0; p < n_p; ++p) {
         SearchGeo& g = s->h_geo[p];
-        g.px = pos[3 * p]; g.py = pos[3 * p + 1]; g.pz = pos[3 * p + 2];
+        g.px = geo[p].px; g.py = geo[p].py; g.pz = geo[p].pz;
         g.vx = vel[3 * p]; g.vy = vel[3 * p + 1]; g.vz = vel[3 * p + 2];
-        g.dt = t_pulses[p] - mean; g.pad = 0.0;
+        g.dt = geo[p].dt; g.pad = 0.0;
     }
     memcpy(s->h_hyps, vel_hyps, (size_t)n_hyp * 3 * sizeof(double));
     SCK(hipMemcpyAsync(s->geo, s->h_geo, (size_t)n_p * sizeof(SearchGeo), hipMemcpyHostToDevice, st));
@@ -322,7 +235,7 @@ hipError_t tdbp_search(Tdbp* t, const float2* raw, const double* pos, const doub
     SCK(tdbp_ensure_axes(t, scene_size, st));
     // pulse chunks: enough workgroups to fill the device several times over, never fewer than 32 pulses each; fewer chunks with
     // more hypotheses, so the partial images stay near 16384 workgroups x 4 KiB
-    const int tiles = ((v.nx + 15) / 16) * ((v.ny + 15) / 16);
+    const int tiles = ((t->nx + 15) / 16) * ((t->ny + 15) / 16);
     if (chunks < 1) {
         const long long blocks = (long long)tiles * n_hyp;
         chunks = (int)((16384 + blocks - 1) / blocks);
@@ -333,30 +246,23 @@ hipError_t tdbp_search(Tdbp* t, const float2* raw, const double* pos, const doub
     if (chunks < 1) chunks = 1;
     const int per_chunk = (n_p + chunks - 1) / chunks;
     chunks = (n_p + per_chunk - 1) / per_chunk;
-    const size_t n_pix = (size_t)v.nx * v.ny;
-    SCK(grow(&s->part, &s->part_cap, (size_t)n_hyp * chunks * n_pix));
+    SCK(grow(&s->part, &s->part_cap, (size_t)n_hyp * chunks * t->nx * t->ny));
     SearchArgs a{};
-    a.rc = v.rc; a.geo = s->geo; a.hyps = s->hyps; a.xax = v.xax; a.yax = v.yax; a.part = s->part;
-    a.inv_c = 1.0 / v.k.c; a.fc = v.k.fc; a.fs = v.k.fs; a.t_start = t_start;
-    a.k_shift = -v.k.fc * 2.0 / v.k.c / v.k.k_rate;
-    a.inv_ns = 1.0 / (double)v.n_s; a.half_w = (float)v.n_s / 2.0f;
-    a.n_p = n_p; a.n_s = v.n_s; a.nx = v.nx; a.ny = v.ny; a.per_chunk = per_chunk; a.chunks = chunks;
+    tdbp_fill_args(t, t_start, per_chunk, a);
+    a.geo = s->geo; a.hyps = s->hyps; a.part = s->part; a.chunks = chunks;
     const dim3 grid(tiles, chunks, n_hyp);
     if (tile) hipLaunchKernelGGL(tdbp_search_tile_kernel, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(tdbp_search_kernel, grid, dim3(256), 0, st, a);
     SCK(hipGetLastError());
     s->route = tile ? 1 : 0;
-    return launch_metric(v, s->part, chunks, n_hyp, d_images, d_records, st);
+    return launch_metric(t, s->part, chunks, n_hyp, d_images, d_records, st);
 }
 
 hipError_t tdbp_search_metric(Tdbp* t, const double2* d_stack, int n_hyp, sarx_tdbp_search_record* d_records, hipStream_t st) {
-    return launch_metric(tdbp_view(t), d_stack, 1, n_hyp, nullptr, d_records, st);
+    return launch_metric(t, d_stack, 1, n_hyp, nullptr, d_records, st);
 }
 
-int tdbp_search_route(const Tdbp* t) {
-    const TdbpSearch* s = tdbp_search_slot(const_cast<Tdbp*>(t));
-    return s ? s->route : -1;
-}
+int tdbp_search_route(const Tdbp* t) { return t->search ? t->search->route : -1; }
 
 hipError_t tdbp_search_staging(Tdbp* t, int n_hyp, bool images, sarx_tdbp_search_record** d_records, double2** d_images, hipStream_t st) {
     TdbpSearch* s = nullptr;
@@ -365,8 +271,7 @@ hipError_t tdbp_search_staging(Tdbp* t, int n_hyp, bool images, sarx_tdbp_search
     *d_records = s->rec;
     *d_images = nullptr;
     if (images) {
-        const TdbpView v = tdbp_view(t);
-        SCK(grow(&s->stack, &s->stack_cap, (size_t)n_hyp * v.nx * v.ny));
+        SCK(grow(&s->stack, &s->stack_cap, (size_t)n_hyp * t->nx * t->ny));
         *d_images = s->stack;
     }
     return hipSuccess;
