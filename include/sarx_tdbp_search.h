@@ -20,8 +20,9 @@
  *    scratch        : belongs to the plan; it grows on the first call of a given n_hyp, a repeated call allocates nothing on the
  *                     device.  As with sarx_tdbp_focus_dev, a plan serves one lane at a time.
  *
- * Left out: an estimate of the radial (ground-range) velocity component (a mismatch there displaces the target instead of
- * defocusing it), normalising the sums when the target leaves the chip, a search per tracker report, and taking the estimate
+ * The radial (ground-range) velocity component is not estimated here (a mismatch there displaces the target instead of defocusing
+ * it): it is measured from the second receive channel, include/sarx_tdbp_pair.h.
+ * Left out: normalising the sums when the target leaves the chip, a search per tracker report, and taking the estimate
  * without a host read of the records. */
 #ifndef SARX_TDBP_SEARCH_H
 #define SARX_TDBP_SEARCH_H

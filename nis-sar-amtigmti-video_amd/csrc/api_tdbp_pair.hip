@@ -1,0 +1,108 @@
+// libsarx C ABI of include/sarx_tdbp_pair.h: argument checks and the launches of tdbp_pair.hip.
+#include "../../include/sarx_tdbp_pair.h"
+#include "api_ctx.h"
+#include "tdbp_pair.h"
+
+#include <cmath>
+
+using namespace sarx;
+
+// what can be said of the parameter block alone; n_pulses < 0: the pulse count is not known yet, the upper end is checked later
+static int params_check(sarx_ctx* c, int n_pulses, const sarx_tdbp_pair_params* k) {
+    if (!k) return fail(c, SARX_ERR_INVALID, "NULL pointer");
+    if (!std::isfinite(k->rx_offset_m[0]) || !std::isfinite(k->rx_offset_m[1])) return fail(c, SARX_ERR_INVALID, "rx_offset_m must be finite");
+    if (!std::isfinite(k->chirp_centre_s)) return fail(c, SARX_ERR_INVALID, "chirp_centre_s must be finite");
+    if (k->n_used < 1) return fail(c, SARX_ERR_INVALID, "n_used %d must be >= 1", k->n_used);
+    for (int ch = 0; ch < 2; ++ch) {
+        if (k->first_pulse[ch] < 0) return fail(c, SARX_ERR_INVALID, "first_pulse[%d] = %d must be >= 0", ch, k->first_pulse[ch]);
+        if (n_pulses >= 0 && (long long)k->first_pulse[ch] + k->n_used > n_pulses)
+            return fail(c, SARX_ERR_INVALID, "channel %d: pulses %d .. %lld lie outside [0, %d]", ch, k->first_pulse[ch],
+                        (long long)k->first_pulse[ch] + k->n_used, n_pulses);
+    }
+    return SARX_OK;
+}
+
+// Everything that can be refused without reading the plan is refused first, so a caller without a device gets the same answers.
+// The plan next: NULL, or not (or no longer) one that sarx_tdbp_plan_create returned.  Last what needs the plan's pulse count: the
+// upper end of the pulse ranges and the rows of vel_tx.  *c: where the message goes.
+static int pair_check(sarx_tdbp_plan* p, bool pointers_ok, const double* vel_tx, const double* vel_focus, double scene_size,
+                      const sarx_tdbp_pair_params* k, const void* img128, const void* img64, sarx_ctx** c) {
+    const bool live = tdbp_plan_live(p);
+    *c = live ? p->ctx : nullptr;
+    if (!pointers_ok) return fail(*c, SARX_ERR_INVALID, "NULL pointer");
+    if (!img128 && !img64) return fail(*c, SARX_ERR_INVALID, "both outputs are NULL");
+    if (((uintptr_t)img128 & 15) || ((uintptr_t)img64 & 7)) return fail(*c, SARX_ERR_INVALID, "misaligned images128 (16) or images64 (8)");
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(vel_focus[i])) return fail(*c, SARX_ERR_INVALID, "vel_focus has a non-finite component");
+    if (!(scene_size > 0 && std::isfinite(scene_size))) return fail(*c, SARX_ERR_INVALID, "scene_size must be positive");
+    const int rc = params_check(*c, -1, k);
+    if (rc != SARX_OK) return rc;
+    if (!p) return fail(nullptr, SARX_ERR_INVALID, "plan is NULL");
+    if (!live) return fail(nullptr, SARX_ERR_INVALID, "plan is not a live sarx_tdbp_plan (destroyed?)");
+    const int rc2 = params_check(*c, p->n_p, k);
+    if (rc2 != SARX_OK) return rc2;
+    for (int i = 0; i < p->n_p; ++i) {
+        const double v2 = vel_tx[3 * i] * vel_tx[3 * i] + vel_tx[3 * i + 1] * vel_tx[3 * i + 1] + vel_tx[3 * i + 2] * vel_tx[3 * i + 2];
+        if (!(v2 > 0 && std::isfinite(v2))) return fail(*c, SARX_ERR_INVALID, "vel_tx row %d is zero or not finite", i);
+    }
+    hipSetDevice(p->ctx->device);
+    return SARX_OK;
+}
+
+extern "C" {
+
+int sarx_tdbp_pair_check(int n_pulses, const sarx_tdbp_pair_params* params) {
+    if (n_pulses < 1) return fail(nullptr, SARX_ERR_INVALID, "n_pulses %d must be >= 1", n_pulses);
+    return params_check(nullptr, n_pulses, params);
+}
+
+int sarx_tdbp_pair_dev(sarx_tdbp_plan* p, const void* d_raw0, const void* d_raw1, const double* pos_tx, const double* vel_tx,
+                       const double* t_pulses, double t_start, const double* vel_focus, double scene_size,
+                       const sarx_tdbp_pair_params* params, void* d_images128, void* d_images64) {
+    sarx_ctx* c = nullptr;
+    const int rc = pair_check(p, d_raw0 && d_raw1 && pos_tx && vel_tx && t_pulses && vel_focus && params, vel_tx, vel_focus, scene_size,
+                              params, d_images128, d_images64, &c);
+    if (rc != SARX_OK) return rc;
+    return guarded(c, [&] {
+        HIPCHK(c, tdbp_pair(p->t, (const float2*)d_raw0, (const float2*)d_raw1, pos_tx, vel_tx, t_pulses, t_start, vel_focus, scene_size,
+                            params, p->search_chunks, (double2*)d_images128, (float2*)d_images64, c->stream));
+        return (int)SARX_OK;
+    });
+}
+
+int sarx_tdbp_pair_host(sarx_tdbp_plan* p, const void* raw0, const void* raw1, const double* pos_tx, const double* vel_tx,
+                        const double* t_pulses, double t_start, const double* vel_focus, double scene_size,
+                        const sarx_tdbp_pair_params* params, void* images128, void* images64) {
+    sarx_ctx* c = nullptr;
+    const int rc = pair_check(p, raw0 && raw1 && pos_tx && vel_tx && t_pulses && vel_focus && params, vel_tx, vel_focus, scene_size, params,
+                              images128, images64, &c);
+    if (rc != SARX_OK) return rc;
+    return guarded(c, [&] {
+        const size_t n = (size_t)p->n_p * p->n_s, n_pix = (size_t)p->nx * p->ny;
+        if (!p->d_raw) HIPCHK(c, hipMalloc(&p->d_raw, n * sizeof(float2)));
+        float2* d_raw1 = nullptr;
+        double2* d_128 = nullptr;
+        float2* d_64 = nullptr;
+        HIPCHK(c, tdbp_pair_staging(p->t, &d_raw1, &d_128, &d_64));
+        HIPCHK(c, staged_copy(c, p->d_raw, raw0, n * sizeof(float2), true));
+        HIPCHK(c, staged_copy(c, d_raw1, raw1, n * sizeof(float2), true));
+        HIPCHK(c, tdbp_pair(p->t, p->d_raw, d_raw1, pos_tx, vel_tx, t_pulses, t_start, vel_focus, scene_size, params, p->search_chunks,
+                            images128 ? d_128 : nullptr, images64 ? d_64 : nullptr, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (images128) HIPCHK(c, staged_copy(c, images128, d_128, 2 * n_pix * sizeof(double2), false));
+        if (images64) HIPCHK(c, staged_copy(c, images64, d_64, 2 * n_pix * sizeof(float2), false));
+        return (int)SARX_OK;
+    });
+}
+
+int sarx_tdbp_pair_route(const sarx_tdbp_plan* p, int* tile) {
+    if (!tile) return fail(nullptr, SARX_ERR_INVALID, "NULL pointer");
+    if (!p) return fail(nullptr, SARX_ERR_INVALID, "plan is NULL");
+    if (!tdbp_plan_live(p)) return fail(nullptr, SARX_ERR_INVALID, "plan is not a live sarx_tdbp_plan (destroyed?)");
+    const int r = tdbp_pair_route(p->t);
+    if (r < 0) return fail(p->ctx, SARX_ERR_INVALID, "the plan has not run a pair call yet");
+    *tile = r;
+    return SARX_OK;
+}
+
+}  // extern "C"

@@ -118,6 +118,7 @@ void tdbp_destroy(Tdbp* t) {
     }
     hipFree(t->part); hipFree(t->img);
     tdbp_search_free(t->search);
+    tdbp_pair_free(t->pair);
     delete t;
 }
 

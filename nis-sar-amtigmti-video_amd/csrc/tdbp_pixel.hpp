@@ -111,4 +111,93 @@ template <class A> __device__ __forceinline__ void tdbp_tile_pixel(const A& c, c
     tdbp_sample(c, xn, tau, p, acc_re, acc_im);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The two-receiver pair (tdbp_pair.hip): receiver c rides at pos_tx + off_c v^ (sar_ati_dcpa_sim_csa.py:145-159),
+// there is no stop-and-go receiver and no t_shift.  d, s_tx, inv_d, d_tx are the transmit leg, computed once per pixel and pulse
+// for both channels; dv = d . v^.
+//   d_rx^2 = d_tx^2 - 2 off dv + off^2 = d_tx^2 (1 - e),  e = off (2 dv - off) / d_tx^2,  |e| <= 2 |off| / d_tx + (off / d_tx)^2.
+// SERIES: sqrt(1 - e) by the series of tdbp_exact_pixel; its first omitted term is 7 e^5 / 256, and the launcher takes this form
+// only when 7 e_max^5 / 256 * d_max < 1e-9 m over all pulses (tdbp_pair_series_ok: e ~ 5e-6 at the reference geometry, where the
+// term is 1e-23 m); otherwise the plain square root runs.
+// A: the kernel's arguments (inv_c, t_start, chirp_centre, fs, inv_ns); PairChan: what tdbp_sample reads of one channel.
+// ------------------------------------------------------------------------------------------------------------
+struct PairChan {
+    const cf* rc;            // [n_p][n_s] range-compressed pulses of this channel
+    double fc;
+    float half_w;
+    int n_s;
+};
+
+template <bool SERIES, class A> __device__ __forceinline__ void tdbp_pair_pixel(const A& c, const PairChan& ch, double s_tx, double inv_d,
+                                                                              double d_tx, double dv, double off, int p, double& acc_re,
+                                                                              double& acc_im) {
+    double d_rx;
+    if (SERIES) {
+        const double eps = off * (2.0 * dv - off) * (inv_d * inv_d);
+        const double sq = fma(eps, fma(eps, fma(eps, fma(eps, -5.0 / 128.0, -1.0 / 16.0), -1.0 / 8.0), -0.5), 1.0);
+        d_rx = d_tx * sq;
+    } else {
+        d_rx = sqrt(fma(off, off - 2.0 * dv, s_tx));
+    }
+    const double tau = (d_tx + d_rx) * c.inv_c;
+    const double idx_f = (tau - c.t_start + c.chirp_centre) * c.fs;
+    const float xn = (float)(2.0 * (idx_f * c.inv_ns) - 1.0);
+    tdbp_sample(ch, xn, tau, p, acc_re, acc_im);
+}
+
+// The pair with the geometry expanded about the tile's reference pixel, as tdbp_tile_prologue / tdbp_tile_pixel do it: per
+// (tile, pulse) one lane computes, with D the vector from the transmitter to the reference pixel and q the pixel's offset from it,
+//   d_tx = d0 sqrt(1 + u),  u = (2 D.q + |q|^2) / d0^2            as d0 (1 + u/2 - u^2/8 + u^3/16), the series of tdbp_tile_pixel
+//   d_tx - d_rx(c) = E_c0 + grad E_c . q                          E_c0 = off (2 D.v^ - off) / (d0 + d_rx0) (no cancellation),
+//                                                                 grad E_c = u^_tx - u^_rx = (off d0 v^ - E_c0 D) / (d0 d_rx0)
+// The remainder of the second line is q^T (H(d) - H(d - off v^)) q / 2 with H the Hessian of the Euclidean norm; the third
+// derivative of the norm at x applied to (h, h, k), unit h and k, is (-(1 - a^2) b - 2 a h_perp . k_perp) / |x|^2 with a = h . x^,
+// b = k . x^, whose modulus is at most sqrt((1 - a^2)(1 + 3 a^2)) <= 2 / sqrt(3).  So |remainder| <= |q|^2 |off| / (sqrt(3) d^2),
+// d the nearest range less |off|; the launcher takes this form only when that and the d_tx series' omitted term both stay below
+// 1e-9 m over all pulses and both channels (tdbp_tile_ok, pair_tile_ok), otherwise the exact form above.
+struct __attribute__((aligned(16))) PairTilePulse {
+    double a1, a2;           // 2 Dx, 2 Dy
+    double inv_d0sq, d0;
+    double e0[2], ex[2], ey[2];
+};
+static_assert(sizeof(PairTilePulse) == 80, "five 16-byte LDS reads per pulse");
+
+// d: from the transmitter to the reference pixel moved with the focus velocity; u: v^ of this pulse
+__device__ __forceinline__ PairTilePulse tdbp_pair_tile_prologue(double dx, double dy, double dz, double ux, double uy, double uz, double off0,
+                                                                double off1) {
+    const double s0 = fma(dx, dx, fma(dy, dy, dz * dz));
+    const double inv_d = rsqrt(s0), d0 = s0 * inv_d;
+    const double dv = ux * dx + uy * dy + uz * dz;
+    PairTilePulse t;
+    t.a1 = 2.0 * dx; t.a2 = 2.0 * dy; t.inv_d0sq = inv_d * inv_d; t.d0 = d0;
+    const double off[2] = {off0, off1};
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const double d_rx = sqrt(fma(off[c], off[c] - 2.0 * dv, s0));
+        const double e0 = off[c] * (2.0 * dv - off[c]) / (d0 + d_rx);
+        const double inv = 1.0 / (d0 * d_rx);
+        t.e0[c] = e0;
+        t.ex[c] = (off[c] * d0 * ux - e0 * dx) * inv;
+        t.ey[c] = (off[c] * d0 * uy - e0 * dy) * inv;
+    }
+    return t;
+}
+
+// d_tx of one pixel and pulse, for both channels
+__device__ __forceinline__ double tdbp_pair_tile_dtx(const PairTilePulse& t, double qx, double qy, double q2) {
+    const double u = fma(t.a1, qx, fma(t.a2, qy, q2)) * t.inv_d0sq;
+    const double h = u * fma(u, fma(u, 1.0 / 16.0, -1.0 / 8.0), 0.5);
+    return fma(t.d0, h, t.d0);
+}
+
+template <class A> __device__ __forceinline__ void tdbp_pair_tile_pixel(const A& c, const PairChan& ch, const PairTilePulse& t, int chan,
+                                                                      double d_tx, double qx, double qy, double two_inv_ns, int p,
+                                                                      double& acc_re, double& acc_im) {
+    const double e = fma(t.ex[chan], qx, fma(t.ey[chan], qy, t.e0[chan]));                  // d_tx - d_rx
+    const double tau = fma(2.0, d_tx, -e) * c.inv_c;
+    const double idx_f = (tau - c.t_start + c.chirp_centre) * c.fs;
+    const float xn = (float)fma(idx_f, two_inv_ns, -1.0);
+    tdbp_sample(ch, xn, tau, p, acc_re, acc_im);
+}
+
 }  // namespace sarx

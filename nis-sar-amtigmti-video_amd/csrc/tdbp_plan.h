@@ -1,9 +1,10 @@
-// The back-projection plan itself: what tdbp.hip and the focus-velocity search (tdbp_search.hip) share and no other unit sees.
+// The back-projection plan itself: what tdbp.hip, the focus-velocity search (tdbp_search.hip) and the two-receiver pair (tdbp_pair.hip) share and no other unit sees.
 #pragma once
 #include <map>
 #include <vector>
 
 #include "tdbp_pixel.hpp"
+#include "tdbp_pair.h"
 #include "tdbp_search.h"
 
 namespace sarx {
@@ -36,6 +37,7 @@ struct Tdbp {
     double2 *part = nullptr, *img = nullptr;
     uint64_t bytes = 0;
     TdbpSearch* search = nullptr; // scratch of the focus-velocity search (tdbp_search.hip), made by its first call, freed by tdbp_destroy
+    TdbpPair* pair = nullptr;     // scratch of the two-receiver pair (tdbp_pair.hip), likewise
 };
 
 hipError_t tdbp_range_compress(Tdbp* t, const float2* raw, int lo, int hi, hipStream_t st);

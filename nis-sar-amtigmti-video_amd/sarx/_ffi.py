@@ -353,6 +353,22 @@ TDBP_SEARCH_SIGNATURES = {
     "sarx_tdbp_search_metric_dev": (_i, [_vp, _vp, _i, _vp]),
 }
 
+# include/sarx_tdbp_pair.h: the two-receiver back-projection, an eleventh table bound the same way
+
+
+class TdbpPairParams(C.Structure):
+    """sarx_tdbp_pair_params (40 bytes)"""
+    _fields_ = [("rx_offset_m", C.c_double * 2), ("chirp_centre_s", C.c_double), ("first_pulse", C.c_int32 * 2), ("n_used", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+TDBP_PAIR_SIGNATURES = {
+    "sarx_tdbp_pair_check": (_i, [_i, _P(TdbpPairParams)]),
+    "sarx_tdbp_pair_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _P(TdbpPairParams), _vp, _vp]),
+    "sarx_tdbp_pair_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _P(TdbpPairParams), _vp, _vp]),
+    "sarx_tdbp_pair_route": (_i, [_vp, _P(_i)]),
+}
+
 _lib = None
 
 
@@ -367,7 +383,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
             list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()) + \
-            list(CLUSTER_SIGNATURES.items()) + list(ATIGATE_SIGNATURES.items()) + list(TDBP_SEARCH_SIGNATURES.items()):
+            list(CLUSTER_SIGNATURES.items()) + list(ATIGATE_SIGNATURES.items()) + list(TDBP_SEARCH_SIGNATURES.items()) + \
+            list(TDBP_PAIR_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
