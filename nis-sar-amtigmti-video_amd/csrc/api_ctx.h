@@ -84,11 +84,20 @@ struct sarx_tdbp_plan {                // made and destroyed by api_focus.hip
 
 namespace sarx {
 
-// the plans alive (api_tdbp_search.hip), so that an entry point can refuse a destroyed one without reading it
+// the plans alive (api_focus.hip, beside their creation), so that an entry point can refuse a destroyed one without reading it
 void tdbp_plan_register(const sarx_tdbp_plan* p, bool alive);      // sarx_tdbp_plan_create / _destroy
 bool tdbp_plan_live(const sarx_tdbp_plan* p);
 extern thread_local std::string g_init_error;     // what sarx_last_error(NULL) returns: failures before a context exists (api_ctx.hip)
 int fail(sarx_ctx* c, int code, const char* fmt, ...);
+// The plan's turn in an entry point's refusals, after everything that needs no plan and before what needs its pulse count: NULL, or
+// not (or no longer) one that sarx_tdbp_plan_create returned.  A usable plan's device is made current and *c is its context.
+inline int tdbp_plan_usable(const sarx_tdbp_plan* p, sarx_ctx** c) {
+    if (!p) return fail(nullptr, SARX_ERR_INVALID, "plan is NULL");
+    if (!tdbp_plan_live(p)) return fail(nullptr, SARX_ERR_INVALID, "plan is not a live sarx_tdbp_plan (destroyed?)");
+    *c = p->ctx;
+    hipSetDevice(p->ctx->device);
+    return SARX_OK;
+}
 #define HIPCHK(c, call)                                                                        \
     do {                                                                                       \
         hipError_t e_ = (call);                                                                \
@@ -96,6 +105,12 @@ int fail(sarx_ctx* c, int code, const char* fmt, ...);
             return fail((c), SARX_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 #define NEED_CTX(c) do { if (!(c)) return fail(nullptr, SARX_ERR_INVALID, "ctx is NULL"); hipSetDevice((c)->device); } while (0)
+// p->d_raw, the device staging [n_p][n_s] of the host entry points' raw pulses, made by the first of them
+inline int tdbp_plan_raw(sarx_ctx* c, sarx_tdbp_plan* p) {
+    const size_t n = (size_t)p->n_p * p->n_s;
+    if (!p->d_raw) HIPCHK(c, hipMalloc(&p->d_raw, n * sizeof(float2)));
+    return SARX_OK;
+}
 
 // No C++ exception crosses the C ABI: entry points that allocate on the host (new, std::vector, std::string) run their body through
 // this guard; std::bad_alloc becomes SARX_ERR_NOMEM, anything else SARX_ERR_DEVICE, the message is set without allocating again.

@@ -7,10 +7,24 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
 using namespace sarx;
+
+// the back-projection plans alive, for the entry points that refuse a destroyed one (tdbp_plan_usable, api_ctx.h)
+static std::mutex g_plans_mu;
+static std::set<const sarx_tdbp_plan*> g_plans;
+void sarx::tdbp_plan_register(const sarx_tdbp_plan* p, bool alive) {
+    std::lock_guard<std::mutex> lk(g_plans_mu);
+    if (alive) g_plans.insert(p); else g_plans.erase(p);
+}
+bool sarx::tdbp_plan_live(const sarx_tdbp_plan* p) {
+    std::lock_guard<std::mutex> lk(g_plans_mu);
+    return p && g_plans.count(p) != 0;
+}
 
 extern "C" {
 
@@ -240,7 +254,7 @@ int sarx_echo_spotlight_dev(sarx_ctx* c, const double* tau_pb, const float* amp_
 }
 
 // ---- time-domain back-projection ---------------------------------------------------------
-// struct sarx_tdbp_plan: api_ctx.h (api_tdbp_search.hip takes plans too, and keeps the list of live ones)
+// struct sarx_tdbp_plan: api_ctx.h (api_tdbp_search.hip and api_tdbp_pair.hip take plans too); the list of live ones: the head of this file
 
 static int sarx_tdbp_plan_create_impl(sarx_ctx* c, int n_pulses, int num_samples, int nx, int ny, const sarx_tdbp_params* k,
                           sarx_tdbp_plan** out) {
@@ -298,7 +312,7 @@ int sarx_tdbp_focus_host(sarx_tdbp_plan* p, const void* raw, const double* pos, 
     if (!raw || !pos || !vel || !t_pulses || !vel_focus || !image) return fail(c, SARX_ERR_INVALID, "NULL pointer");
     if (!(scene_size > 0)) return fail(c, SARX_ERR_INVALID, "scene_size must be positive");
     const size_t n = (size_t)p->n_p * p->n_s;
-    if (!p->d_raw) HIPCHK(c, hipMalloc(&p->d_raw, n * sizeof(float2)));
+    if (const int rc = tdbp_plan_raw(c, p)) return rc;
     HIPCHK(c, staged_copy(c, p->d_raw, raw, n * sizeof(float2), true));
     HIPCHK(c, tdbp_focus(p->t, p->d_raw, pos, vel, t_pulses, t_start, vel_focus, scene_size, range_compressed != nullptr, c->stream));
     HIPCHK(c, hipMemcpyAsync(image, tdbp_image(p->t), (size_t)p->nx * p->ny * sizeof(double2), hipMemcpyDeviceToHost, c->stream));

@@ -27,8 +27,7 @@ static int params_check(sarx_ctx* c, int n_pulses, const sarx_tdbp_pair_params* 
 // upper end of the pulse ranges and the rows of vel_tx.  *c: where the message goes.
 static int pair_check(sarx_tdbp_plan* p, bool pointers_ok, const double* vel_tx, const double* vel_focus, double scene_size,
                       const sarx_tdbp_pair_params* k, const void* img128, const void* img64, sarx_ctx** c) {
-    const bool live = tdbp_plan_live(p);
-    *c = live ? p->ctx : nullptr;
+    *c = tdbp_plan_live(p) ? p->ctx : nullptr;
     if (!pointers_ok) return fail(*c, SARX_ERR_INVALID, "NULL pointer");
     if (!img128 && !img64) return fail(*c, SARX_ERR_INVALID, "both outputs are NULL");
     if (((uintptr_t)img128 & 15) || ((uintptr_t)img64 & 7)) return fail(*c, SARX_ERR_INVALID, "misaligned images128 (16) or images64 (8)");
@@ -37,15 +36,13 @@ static int pair_check(sarx_tdbp_plan* p, bool pointers_ok, const double* vel_tx,
     if (!(scene_size > 0 && std::isfinite(scene_size))) return fail(*c, SARX_ERR_INVALID, "scene_size must be positive");
     const int rc = params_check(*c, -1, k);
     if (rc != SARX_OK) return rc;
-    if (!p) return fail(nullptr, SARX_ERR_INVALID, "plan is NULL");
-    if (!live) return fail(nullptr, SARX_ERR_INVALID, "plan is not a live sarx_tdbp_plan (destroyed?)");
+    if (const int rc1 = tdbp_plan_usable(p, c)) return rc1;
     const int rc2 = params_check(*c, p->n_p, k);
     if (rc2 != SARX_OK) return rc2;
     for (int i = 0; i < p->n_p; ++i) {
         const double v2 = vel_tx[3 * i] * vel_tx[3 * i] + vel_tx[3 * i + 1] * vel_tx[3 * i + 1] + vel_tx[3 * i + 2] * vel_tx[3 * i + 2];
         if (!(v2 > 0 && std::isfinite(v2))) return fail(*c, SARX_ERR_INVALID, "vel_tx row %d is zero or not finite", i);
     }
-    hipSetDevice(p->ctx->device);
     return SARX_OK;
 }
 
@@ -79,7 +76,7 @@ int sarx_tdbp_pair_host(sarx_tdbp_plan* p, const void* raw0, const void* raw1, c
     if (rc != SARX_OK) return rc;
     return guarded(c, [&] {
         const size_t n = (size_t)p->n_p * p->n_s, n_pix = (size_t)p->nx * p->ny;
-        if (!p->d_raw) HIPCHK(c, hipMalloc(&p->d_raw, n * sizeof(float2)));
+        if (const int rc = tdbp_plan_raw(c, p)) return rc;
         float2* d_raw1 = nullptr;
         double2* d_128 = nullptr;
         float2* d_64 = nullptr;
@@ -97,10 +94,10 @@ int sarx_tdbp_pair_host(sarx_tdbp_plan* p, const void* raw0, const void* raw1, c
 
 int sarx_tdbp_pair_route(const sarx_tdbp_plan* p, int* tile) {
     if (!tile) return fail(nullptr, SARX_ERR_INVALID, "NULL pointer");
-    if (!p) return fail(nullptr, SARX_ERR_INVALID, "plan is NULL");
-    if (!tdbp_plan_live(p)) return fail(nullptr, SARX_ERR_INVALID, "plan is not a live sarx_tdbp_plan (destroyed?)");
+    sarx_ctx* c = nullptr;
+    if (const int rc = tdbp_plan_usable(p, &c)) return rc;
     const int r = tdbp_pair_route(p->t);
-    if (r < 0) return fail(p->ctx, SARX_ERR_INVALID, "the plan has not run a pair call yet");
+    if (r < 0) return fail(c, SARX_ERR_INVALID, "the plan has not run a pair call yet");
     *tile = r;
     return SARX_OK;
 }

@@ -4,29 +4,15 @@
 #include "tdbp_search.h"
 
 #include <cmath>
-#include <mutex>
-#include <set>
 
 using namespace sarx;
-
-static std::mutex g_plans_mu;
-static std::set<const sarx_tdbp_plan*> g_plans;
-void sarx::tdbp_plan_register(const sarx_tdbp_plan* p, bool alive) {
-    std::lock_guard<std::mutex> lk(g_plans_mu);
-    if (alive) g_plans.insert(p); else g_plans.erase(p);
-}
-bool sarx::tdbp_plan_live(const sarx_tdbp_plan* p) {
-    std::lock_guard<std::mutex> lk(g_plans_mu);
-    return p && g_plans.count(p) != 0;
-}
 
 extern "C" {
 
 // Everything that can be refused without reading the plan is refused first, so a caller without a device gets the same answers.
-// The plan last: NULL, or not (or no longer) one that sarx_tdbp_plan_create returned.  *c: where the message goes.
+// The plan last (tdbp_plan_usable).  *c: where the message goes.
 static int search_check(sarx_tdbp_plan* p, bool pointers_ok, const double* vel_hyps, int n_hyp, const double* scene_size, sarx_ctx** c) {
-    const bool live = tdbp_plan_live(p);
-    *c = live ? p->ctx : nullptr;
+    *c = tdbp_plan_live(p) ? p->ctx : nullptr;
     if (!pointers_ok) return fail(*c, SARX_ERR_INVALID, "NULL pointer");
     if (n_hyp < 1 || n_hyp > SARX_TDBP_SEARCH_MAX_HYP)
         return fail(*c, SARX_ERR_INVALID, "n_hyp %d must be 1 .. %d", n_hyp, SARX_TDBP_SEARCH_MAX_HYP);
@@ -35,10 +21,7 @@ static int search_check(sarx_tdbp_plan* p, bool pointers_ok, const double* vel_h
             if (!std::isfinite(vel_hyps[i]))
                 return fail(*c, SARX_ERR_INVALID, "focus velocity %d has a non-finite component", i / 3);
     if (scene_size && !(*scene_size > 0 && std::isfinite(*scene_size))) return fail(*c, SARX_ERR_INVALID, "scene_size must be positive");
-    if (!p) return fail(nullptr, SARX_ERR_INVALID, "plan is NULL");
-    if (!live) return fail(nullptr, SARX_ERR_INVALID, "plan is not a live sarx_tdbp_plan (destroyed?)");
-    hipSetDevice(p->ctx->device);
-    return SARX_OK;
+    return tdbp_plan_usable(p, c);
 }
 
 int sarx_tdbp_search_dev(sarx_tdbp_plan* p, const void* d_raw, const double* pos, const double* vel, const double* t_pulses,
@@ -63,7 +46,7 @@ int sarx_tdbp_search_host(sarx_tdbp_plan* p, const void* raw, const double* pos,
     if (rc != SARX_OK) return rc;
     return guarded(c, [&] {
         const size_t n = (size_t)p->n_p * p->n_s, n_pix = (size_t)p->nx * p->ny;
-        if (!p->d_raw) HIPCHK(c, hipMalloc(&p->d_raw, n * sizeof(float2)));
+        if (const int rc = tdbp_plan_raw(c, p)) return rc;
         HIPCHK(c, staged_copy(c, p->d_raw, raw, n * sizeof(float2), true));
         sarx_tdbp_search_record* d_rec = nullptr;
         double2* d_img = nullptr;
@@ -79,10 +62,10 @@ int sarx_tdbp_search_host(sarx_tdbp_plan* p, const void* raw, const double* pos,
 
 int sarx_tdbp_search_route(const sarx_tdbp_plan* p, int* tile) {
     if (!tile) return fail(nullptr, SARX_ERR_INVALID, "NULL pointer");
-    if (!p) return fail(nullptr, SARX_ERR_INVALID, "plan is NULL");
-    if (!tdbp_plan_live(p)) return fail(nullptr, SARX_ERR_INVALID, "plan is not a live sarx_tdbp_plan (destroyed?)");
+    sarx_ctx* c = nullptr;
+    if (const int rc = tdbp_plan_usable(p, &c)) return rc;
     const int r = tdbp_search_route(p->t);
-    if (r < 0) return fail(p->ctx, SARX_ERR_INVALID, "the plan has not run a search yet");
+    if (r < 0) return fail(c, SARX_ERR_INVALID, "the plan has not run a search yet");
     *tile = r;
     return SARX_OK;
 }
@@ -90,8 +73,8 @@ int sarx_tdbp_search_route(const sarx_tdbp_plan* p, int* tile) {
 int sarx_tdbp_search_set_chunks(sarx_tdbp_plan* p, int chunks) {
     if (chunks < 0 || chunks > SARX_TDBP_SEARCH_MAX_CHUNKS)
         return fail(tdbp_plan_live(p) ? p->ctx : nullptr, SARX_ERR_INVALID, "chunks %d must be 0 .. %d", chunks, SARX_TDBP_SEARCH_MAX_CHUNKS);
-    if (!p) return fail(nullptr, SARX_ERR_INVALID, "plan is NULL");
-    if (!tdbp_plan_live(p)) return fail(nullptr, SARX_ERR_INVALID, "plan is not a live sarx_tdbp_plan (destroyed?)");
+    sarx_ctx* c = nullptr;
+    if (const int rc = tdbp_plan_usable(p, &c)) return rc;
     p->search_chunks = chunks;
     return SARX_OK;
 }

@@ -16,6 +16,9 @@
 //     one pixel and pulse is tdbp_pixel.hpp's, which the focus-velocity search (tdbp_search.hip) runs too.
 //     Compute-bound in fp64 (one rsqrt + a short series instead of two square roots and a division):
 //     6.6e8 pixel-pulses per 512 x 512 x 2500 frame in 1.66 ms.
+//   3 what the search and the two-receiver pair (tdbp_pair.hip) share with the focus on the host, stated here once (tdbp_plan.h):
+//     tdbp_range_compress into a destination the caller names, the geometry bounds (moved_rect_range, tdbp_clamp_window,
+//     tdbp_tile_reach), the pulse chunks of one call (tdbp_pick_chunks) and the scratch either holds beside the plan (TdbpScratch).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -49,11 +52,8 @@ __global__ __launch_bounds__(256) void wrap_copy_kernel(const cf* in, int rows, 
 }
 
 __global__ __launch_bounds__(256) void tdbp_kernel(TdbpArgs a) {
-    const int tiles_x = (a.nx + 15) >> 4;
-    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const int ix = tx * 16 + (threadIdx.x & 15), iy = ty * 16 + (threadIdx.x >> 4);
-    const bool live = ix < a.nx && iy < a.ny;
-    const double gx0 = a.xax[live ? ix : 0], gy0 = a.yax[live ? iy : 0];
+    const TdbpPix px = tdbp_pix(a.nx, a.ny);
+    const double gx0 = a.xax[px.live ? px.ix : 0], gy0 = a.yax[px.live ? px.iy : 0];
     const int p0 = blockIdx.y * a.per_chunk, p1 = min(a.n_p, p0 + a.per_chunk);
     double acc_re = 0.0, acc_im = 0.0;
     for (int p = p0; p < p1; ++p) {
@@ -64,20 +64,15 @@ __global__ __launch_bounds__(256) void tdbp_kernel(TdbpArgs a) {
         const double dz = a.vfz * g.dt - g.pz;
         tdbp_exact_pixel(a, dx, dy, dz, g.wx, g.wy, g.wz, g.pad, p, acc_re, acc_im);
     }
-    if (live) a.part[(size_t)blockIdx.y * a.nx * a.ny + (size_t)iy * a.nx + ix] = make_double2(acc_re, acc_im);
+    if (px.live) a.part[(size_t)blockIdx.y * a.nx * a.ny + (size_t)px.iy * a.nx + px.ix] = make_double2(acc_re, acc_im);
 }
 
 // the tile form (tdbp_pixel.hpp): one lane per pulse fills the batch's records, then every pixel walks them
 __global__ __launch_bounds__(256) void tdbp_tile_kernel(TdbpArgs a) {
     __shared__ TilePulse s_tp[TP_BATCH];
-    const int tiles_x = (a.nx + 15) >> 4;
-    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const int ix = tx * 16 + (threadIdx.x & 15), iy = ty * 16 + (threadIdx.x >> 4);
-    const bool live = ix < a.nx && iy < a.ny;
-    const double xc = a.xax[min(tx * 16 + 8, a.nx - 1)], yc = a.yax[min(ty * 16 + 8, a.ny - 1)];
-    const double qx = a.xax[live ? ix : 0] - xc, qy = a.yax[live ? iy : 0] - yc;
-    const double q2 = fma(qx, qx, qy * qy);
-    const float qxf = (float)qx, qyf = (float)qy;
+    const TdbpPix px = tdbp_pix(a.nx, a.ny);
+    const TdbpTileOffsets o = tdbp_tile_offsets(a.xax, a.yax, px, a.nx, a.ny);
+    const float qxf = (float)o.qx, qyf = (float)o.qy;
     const int p0 = blockIdx.y * a.per_chunk, p1 = min(a.n_p, p0 + a.per_chunk);
     const double two_inv_ns = 2.0 * a.inv_ns;
     double acc_re = 0.0, acc_im = 0.0;
@@ -86,25 +81,19 @@ __global__ __launch_bounds__(256) void tdbp_tile_kernel(TdbpArgs a) {
         __syncthreads();                                   // the previous batch has been consumed
         if ((int)threadIdx.x < nb) {
             const PulseGeo g = a.geo[pb + threadIdx.x];
-            const double dx = fma(a.vfx, g.dt, xc) - g.px, dy = fma(a.vfy, g.dt, yc) - g.py, dz = a.vfz * g.dt - g.pz;   // :205-208 at the reference pixel
+            const double dx = fma(a.vfx, g.dt, o.xc) - g.px, dy = fma(a.vfy, g.dt, o.yc) - g.py, dz = a.vfz * g.dt - g.pz;   // :205-208 at the reference pixel
             s_tp[threadIdx.x] = tdbp_tile_prologue(a, dx, dy, dz, g.wx, g.wy, g.wz, g.pad);
         }
         __syncthreads();
-        for (int k = 0; k < nb; ++k) tdbp_tile_pixel(a, s_tp[k], qx, qy, q2, qxf, qyf, two_inv_ns, pb + k, acc_re, acc_im);
+        for (int k = 0; k < nb; ++k) tdbp_tile_pixel(a, s_tp[k], o.qx, o.qy, o.q2, qxf, qyf, two_inv_ns, pb + k, acc_re, acc_im);
     }
-    if (live) a.part[(size_t)blockIdx.y * a.nx * a.ny + (size_t)iy * a.nx + ix] = make_double2(acc_re, acc_im);
+    if (px.live) a.part[(size_t)blockIdx.y * a.nx * a.ny + (size_t)px.iy * a.nx + px.ix] = make_double2(acc_re, acc_im);
 }
 
 __global__ __launch_bounds__(256) void tdbp_reduce_kernel(const double2* part, int chunks, size_t n_pix, double2* out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_pix) return;
-    double re = 0.0, im = 0.0;
-    for (int c = 0; c < chunks; ++c) {
-        const double2 v = part[(size_t)c * n_pix + i];
-        re += v.x;
-        im += v.y;
-    }
-    out[i] = make_double2(re, im);
+    out[i] = tdbp_sum_chunks(part, chunks, n_pix, i);
 }
 
 void tdbp_destroy(Tdbp* t) {
@@ -121,8 +110,6 @@ void tdbp_destroy(Tdbp* t) {
     tdbp_pair_free(t->pair);
     delete t;
 }
-
-#define TCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 // conj(FFT_m(fftshift(ref_chirp))) (:177-179) for an m-point transform, cached; linspace endpoints as torch builds
 // them (two-sided)
@@ -164,6 +151,7 @@ Tdbp* tdbp_create(int n_pulses, int num_samples, int nx, int ny, const sarx_tdbp
     t->n_p = n_pulses; t->n_s = num_samples; t->nx = nx; t->ny = ny; t->taps = taps; t->m = m; t->blk = m - taps + 1;
     t->k = *k; t->tw_all = tw_all;
     const size_t n_pix = (size_t)nx * ny;
+    // a policy of its own, not tdbp_pick_chunks: fixed when the plan is made, and capped by the bytes of the partial images
     int chunks = (int)(((size_t)1 << 20) / (n_pix ? n_pix : 1));
     if (chunks > n_pulses / 32) chunks = n_pulses / 32;
     if (chunks > 64) chunks = 64;
@@ -196,7 +184,7 @@ Tdbp* tdbp_create(int n_pulses, int num_samples, int nx, int ny, const sarx_tdbp
 }
 
 // outputs [n0, n0 + cnt) of the circular correlation through one m-point transform (cnt <= m - taps + 1)
-static hipError_t compress_block(Tdbp* t, const float2* raw, int n0, int cnt, int m, hipStream_t st) {
+static hipError_t compress_block(Tdbp* t, const float2* raw, cf* dst, int n0, int cnt, int m, hipStream_t st) {
     cf* hhat = nullptr;
     TCK(filter_spectrum(t, m, &hhat));
     const int n = t->n_s;
@@ -205,7 +193,7 @@ static hipError_t compress_block(Tdbp* t, const float2* raw, int n0, int cnt, in
         // registers / LDS, the cnt wanted outputs written to their place (range_pass_kernel<m, RG_CONV>): 0.42 -> 0.185 ms per
         // 2500 x 22004 frame against copy-in, two transforms and copy-out (profiles/r05_bj_*)
         RangeArgs ca{};
-        ca.in = raw; ca.out = t->rc + n0; ca.tw = t->tw_all + m; ca.n_az = t->n_p; ca.inv_n = 1.0f / (float)m;
+        ca.in = raw; ca.out = dst + n0; ca.tw = t->tw_all + m; ca.n_az = t->n_p; ca.inv_n = 1.0f / (float)m;
         ca.mulvec = hhat; ca.mul_period = 1;
         ca.conv_valid = m; ca.conv_crop0 = 0; ca.conv_out = cnt; ca.conv_in_ld = (size_t)n; ca.conv_out_ld = (size_t)n;
         ca.conv_wrap_n = n; ca.conv_wrap_c0 = n0 % n;
@@ -216,12 +204,13 @@ static hipError_t compress_block(Tdbp* t, const float2* raw, int n0, int cnt, in
     TCK(hipGetLastError());
     TCK(line_fft_pow2(t->tw_all, t->work, t->n_p, m, false, st, hhat));      // * conj(reference spectrum) in the epilogue
     TCK(line_fft_pow2(t->tw_all, t->work, t->n_p, m, true, st));
-    return scale_copy_cols(t->work, t->n_p, cnt, m, t->rc + n0, t->n_p, cnt, n, nullptr, 1.0f, st);
+    return scale_copy_cols(t->work, t->n_p, cnt, m, dst + n0, t->n_p, cnt, n, nullptr, 1.0f, st);
 }
 
-// raw: device [n_p][n_s] complex64.  Leaves the range-compressed samples [lo, hi) of every pulse in t->rc
-// (the back-projection of one scene reads a narrow window of each pulse: ~1700 of 22004 samples natively).
-hipError_t tdbp_range_compress(Tdbp* t, const float2* raw, int lo, int hi, hipStream_t st) {
+// raw: device [n_p][n_s] complex64.  Leaves the range-compressed samples [lo, hi) of every pulse in dst [n_p][n_s]: the plan's rc, or
+// the pair's buffer for its second channel (the back-projection of one scene reads a narrow window of each pulse: ~1700 of 22004
+// samples natively).
+hipError_t tdbp_range_compress(Tdbp* t, const float2* raw, cf* dst, int lo, int hi, hipStream_t st) {
     const int n = t->n_s;
     if (lo < 0) lo = 0;
     if (hi > n) hi = n;
@@ -229,23 +218,38 @@ hipError_t tdbp_range_compress(Tdbp* t, const float2* raw, int lo, int hi, hipSt
     if (hi <= lo) return hipSuccess;
     int m = 16;
     while (m < (hi - lo) + t->taps - 1) m <<= 1;
-    if (m < t->m) return compress_block(t, raw, lo, hi - lo, m, st);        // one transform shorter than the plan's
+    if (m < t->m) return compress_block(t, raw, dst, lo, hi - lo, m, st);        // one transform shorter than the plan's
     for (int n0 = lo; n0 < hi; n0 += t->blk) {
         const int cnt = (hi - n0 < t->blk) ? hi - n0 : t->blk;
-        TCK(compress_block(t, raw, n0, cnt, t->m, st));
+        TCK(compress_block(t, raw, dst, n0, cnt, t->m, st));
     }
     return hipSuccess;
 }
 
+// ---- geometry bounds on the host: what the focus, the search and the pair decide their sample window and their kernel with ----
 // Nearest and farthest transmit range of one pulse over the pixel rectangle (half side h) moved by v_f dt: the rectangle is
 // convex, so the range is largest at a corner and smallest at the projection of the platform clamped to the rectangle.
-static void moved_rect_range(const PulseGeo& g, const double* vf, double h, double* dmin, double* dmax) {
+void moved_rect_range(const PulseGeo& g, const double* vf, double h, double* dmin, double* dmax) {
     const double sx = vf[0] * g.dt, sy = vf[1] * g.dt, gz = vf[2] * g.dt - g.pz;
     const double qx = g.px - sx, qy = g.py - sy;                        // platform relative to the moved rectangle
     const double cx = qx < -h ? -h : (qx > h ? h : qx), cy = qy < -h ? -h : (qy > h ? h : qy);
     *dmin = sqrt((cx - qx) * (cx - qx) + (cy - qy) * (cy - qy) + gz * gz);
     const double ax = fabs(qx) + h, ay = fabs(qy) + h;                  // farthest corner
     *dmax = sqrt(ax * ax + ay * ay + gz * gz);
+}
+
+// Sample indices [imin, imax] (fractional) to the window [lo, hi) inside [0, n_s]: x = idx - 0.5 rounded through float32 (< 1 sample
+// at any n_s <= 2^23), i0 = floor(x), i0 + 1 is read too.  A NaN bound gives 0, never a cast of it.
+void tdbp_clamp_window(double imin, double imax, int n_s, int* lo, int* hi) {
+    const double l = floor(imin) - 3.0, u = ceil(imax) + 4.0;
+    *lo = !(l > 0) ? 0 : (l > (double)n_s ? n_s : (int)l);
+    *hi = !(u > 0) ? 0 : (u > (double)n_s ? n_s : (int)u);
+}
+
+// Farthest pixel of a 16 x 16 tile from its reference pixel (index 8 of 16), in metres; negative when the grid is thinner than two pixels
+double tdbp_tile_reach(const Tdbp* t, double scene_size) {
+    if (t->nx < 2 || t->ny < 2) return -1.0;
+    return 8.0 * hypot(scene_size / (double)(t->nx - 1), scene_size / (double)(t->ny - 1));
 }
 
 // Sample window [lo, hi) that the back-projection can touch: a bound, not an estimate.  Per pulse the transmit range lies in
@@ -264,20 +268,16 @@ void tdbp_sample_window(const Tdbp* t, const std::vector<PulseGeo>& geo, const d
         if (a < imin) imin = a;
         if (b > imax) imax = b;
     }
-    // x = idx - 0.5 rounded through float32 (< 1 sample at any n_s <= 2^23), i0 = floor(x), i0 + 1 is read too
-    const double l = floor(imin) - 3.0, u = ceil(imax) + 4.0;
-    *lo = l < 0 ? 0 : (l > (double)t->n_s ? t->n_s : (int)l);
-    *hi = u < 0 ? 0 : (u > (double)t->n_s ? t->n_s : (int)u);
+    tdbp_clamp_window(imin, imax, t->n_s, lo, hi);
 }
 
-// May the tile kernel stand in for the exact one?  Farthest pixel of a 16 x 16 tile from its reference pixel (index 8 of 16) against
-// the nearest range of any pulse: the first omitted series term of d_tx, 5 u^4 / 128 * d, must stay below 1e-9 m (4e-7 rad of
-// carrier phase at X band).  SARX_TDBP_TILE=0 forces the exact kernel (A/B).
+// May the tile kernel stand in for the exact one?  The tile's reach (tdbp_tile_reach) against the nearest range of any pulse: the
+// first omitted series term of d_tx, 5 u^4 / 128 * d, must stay below 1e-9 m (4e-7 rad of carrier phase at X band).
+// SARX_TDBP_TILE=0 forces the exact kernel (A/B).
 bool tdbp_tile_ok(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double scene_size) {
     if (const char* ev = getenv("SARX_TDBP_TILE")) if (atoi(ev) == 0) return false;
-    if (t->nx < 2 || t->ny < 2) return false;
-    const double h = scene_size / 2;
-    const double qm = 8.0 * hypot(scene_size / (double)(t->nx - 1), scene_size / (double)(t->ny - 1));
+    const double h = scene_size / 2, qm = tdbp_tile_reach(t, scene_size);
+    if (qm < 0.0) return false;
     for (const PulseGeo& g : geo) {
         double dmin, dmax;
         moved_rect_range(g, vf, h, &dmin, &dmax);
@@ -286,6 +286,46 @@ bool tdbp_tile_ok(const Tdbp* t, const std::vector<PulseGeo>& geo, const double*
         if (!(5.0 / 128.0 * u * u * u * u * dmax < 1e-9)) return false;
     }
     return true;
+}
+
+// ---- what a call of the search or the pair chooses and holds beside the plan ----
+// Pulse chunks of one call: requested > 0 is the caller's number (sarx_tdbp_search_set_chunks); else enough workgroups to fill the
+// device several times over - 16384 of them, a chunk launching tiles x blocks_per_chunk - and never fewer than 32 pulses each.
+// Returns the chunks that hold a pulse, *per_chunk pulses in each but the last.
+int tdbp_pick_chunks(int tiles, int blocks_per_chunk, int n_pulses, int requested, int* per_chunk) {
+    int chunks = requested;
+    if (chunks < 1) {
+        const long long blocks = (long long)tiles * blocks_per_chunk;
+        chunks = (int)((16384 + blocks - 1) / blocks);
+        if (chunks > n_pulses / 32) chunks = n_pulses / 32;
+    }
+    if (chunks > SARX_TDBP_SEARCH_MAX_CHUNKS) chunks = SARX_TDBP_SEARCH_MAX_CHUNKS;
+    if (chunks > n_pulses) chunks = n_pulses;
+    if (chunks < 1) chunks = 1;
+    *per_chunk = (n_pulses + chunks - 1) / chunks;
+    return (n_pulses + *per_chunk - 1) / *per_chunk;
+}
+
+hipError_t grow(double2** buf, size_t* cap, size_t need) {
+    if (need <= *cap) return hipSuccess;
+    TCK(hipFree(*buf));                                    // waits for the launches that may still read it
+    *buf = nullptr; *cap = 0;
+    TCK(hipMalloc(buf, need * sizeof(double2)));
+    *cap = need;
+    return hipSuccess;
+}
+
+hipError_t tdbp_scratch_init(TdbpScratch* s, int n_p, size_t bytes) {
+    s->bytes = (size_t)n_p * bytes;
+    TCK(hipMalloc(&s->geo, s->bytes));
+    TCK(hipHostMalloc(&s->h_geo, s->bytes, hipHostMallocDefault));
+    return hipEventCreateWithFlags(&s->up_done, hipEventDisableTiming);
+}
+
+void tdbp_scratch_free(TdbpScratch* s) {
+    hipFree(s->geo); hipFree(s->part);
+    if (s->h_geo) hipHostFree(s->h_geo);
+    if (s->up_done) hipEventDestroy(s->up_done);
 }
 
 static void linspace(double a, double b, int n, std::vector<double>& out) {     // numpy.linspace (:173-174)
@@ -338,7 +378,7 @@ hipError_t tdbp_focus(Tdbp* t, const float2* raw, const double* pos, const doubl
     tdbp_set_focus(geo, vel, vel_focus);
     int lo = 0, hi = t->n_s;
     if (!all_samples && !t->full_rc) tdbp_sample_window(t, geo, vel_focus, t_start, scene_size, &lo, &hi);
-    TCK(tdbp_range_compress(t, raw, lo, hi, st));
+    TCK(tdbp_range_compress(t, raw, t->rc, lo, hi, st));
     memcpy(t->h_geo[slot], geo.data(), geo.size() * sizeof(PulseGeo));
     TCK(hipMemcpyAsync(t->geo[slot], t->h_geo[slot], geo.size() * sizeof(PulseGeo), hipMemcpyHostToDevice, st));
     TCK(tdbp_ensure_axes(t, scene_size, st));

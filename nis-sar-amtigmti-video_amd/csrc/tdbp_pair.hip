@@ -2,7 +2,8 @@
 // (sar_ati_dcpa_sim_csa.py:113-178) imaged onto one ground grid in one enqueue.
 //
 //   1 range compression, once per channel: tdbp_range_compress over ONE sample window that bounds what either channel can touch
-//     (pair_sample_window: a bound, not an estimate).  Channel 0 lands in the plan's rc buffer, channel 1 in the scratch's.
+//     (pair_bounds, on the focus's moved_rect_range and tdbp_clamp_window: a bound, not an estimate).  Channel 0 lands in the
+//     plan's rc buffer, channel 1 in the scratch's: tdbp_range_compress takes its destination.
 //   2 back-projection: one thread per pixel carries BOTH channels.  Per pulse the pixel moved with the focus velocity, the
 //     vector to the transmitter, d_tx and its reciprocal square root and d . v^ are computed once; each channel adds only its
 //     receive leg (tdbp_pair_pixel of tdbp_pixel.hpp), the float32 interpolation coordinate and its sample (tdbp_sample).  The
@@ -13,7 +14,7 @@
 // Two forms of the geometry, as in tdbp.hip: the exact one (tdbp_pair_kernel), and the one expanded about the reference pixel of each
 // 16 x 16 tile (tdbp_pair_tile_kernel: one lane per pulse fills a 256-pulse batch of records in LDS, every pixel walks them), taken
 // when tdbp_tile_ok and pair_tile_ok bound its truncation error below 1e-9 m for both channels.  Same pulse order per pixel, same
-// fp64 accumulation.
+// fp64 accumulation.  Pulse chunks: tdbp_pick_chunks (tdbp.hip); pulse table, staging and partial images: a TdbpScratch (tdbp_plan.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -46,11 +47,8 @@ struct PairArgs {
 };
 
 template <bool SERIES> __global__ __launch_bounds__(256) void tdbp_pair_kernel(PairArgs a) {
-    const int tiles_x = (a.nx + 15) >> 4;
-    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const int ix = tx * 16 + (threadIdx.x & 15), iy = ty * 16 + (threadIdx.x >> 4);
-    const bool live = ix < a.nx && iy < a.ny;
-    const double gx0 = a.xax[live ? ix : 0], gy0 = a.yax[live ? iy : 0];
+    const TdbpPix px = tdbp_pix(a.nx, a.ny);
+    const double gx0 = a.xax[px.live ? px.ix : 0], gy0 = a.yax[px.live ? px.iy : 0];
     const int p0 = a.u0 + blockIdx.y * a.per_chunk, p1 = min(a.u1, p0 + a.per_chunk);
     const int e0 = a.first[0] + a.n_used, e1 = a.first[1] + a.n_used;
     double re0 = 0.0, im0 = 0.0, re1 = 0.0, im1 = 0.0;
@@ -66,8 +64,8 @@ template <bool SERIES> __global__ __launch_bounds__(256) void tdbp_pair_kernel(P
         if (p >= a.first[0] && p < e0) tdbp_pair_pixel<SERIES>(a, a.ch[0], s_tx, inv_d, d_tx, dv, a.off[0], p, re0, im0);
         if (p >= a.first[1] && p < e1) tdbp_pair_pixel<SERIES>(a, a.ch[1], s_tx, inv_d, d_tx, dv, a.off[1], p, re1, im1);
     }
-    if (live) {
-        const size_t n_pix = (size_t)a.nx * a.ny, at = (size_t)blockIdx.y * n_pix + (size_t)iy * a.nx + ix;
+    if (px.live) {
+        const size_t n_pix = (size_t)a.nx * a.ny, at = (size_t)blockIdx.y * n_pix + (size_t)px.iy * a.nx + px.ix;
         a.part[at] = make_double2(re0, im0);
         a.part[(size_t)a.chunks * n_pix + at] = make_double2(re1, im1);
     }
@@ -76,13 +74,8 @@ template <bool SERIES> __global__ __launch_bounds__(256) void tdbp_pair_kernel(P
 // the tile form (tdbp_pixel.hpp): one lane per pulse fills the batch's records, then every pixel walks them
 __global__ __launch_bounds__(256) void tdbp_pair_tile_kernel(PairArgs a) {
     __shared__ PairTilePulse s_tp[TP_BATCH];
-    const int tiles_x = (a.nx + 15) >> 4;
-    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const int ix = tx * 16 + (threadIdx.x & 15), iy = ty * 16 + (threadIdx.x >> 4);
-    const bool live = ix < a.nx && iy < a.ny;
-    const double xc = a.xax[min(tx * 16 + 8, a.nx - 1)], yc = a.yax[min(ty * 16 + 8, a.ny - 1)];
-    const double qx = a.xax[live ? ix : 0] - xc, qy = a.yax[live ? iy : 0] - yc;
-    const double q2 = fma(qx, qx, qy * qy);
+    const TdbpPix px = tdbp_pix(a.nx, a.ny);
+    const TdbpTileOffsets o = tdbp_tile_offsets(a.xax, a.yax, px, a.nx, a.ny);
     const int p0 = a.u0 + blockIdx.y * a.per_chunk, p1 = min(a.u1, p0 + a.per_chunk);
     const int e0 = a.first[0] + a.n_used, e1 = a.first[1] + a.n_used;
     const double two_inv_ns = 2.0 * a.inv_ns;
@@ -92,19 +85,19 @@ __global__ __launch_bounds__(256) void tdbp_pair_tile_kernel(PairArgs a) {
         __syncthreads();                                   // the previous batch has been consumed
         if ((int)threadIdx.x < nb) {
             const PairGeo g = a.geo[pb + threadIdx.x];
-            const double dx = fma(a.vfx, g.dt, xc) - g.px, dy = fma(a.vfy, g.dt, yc) - g.py, dz = a.vfz * g.dt - g.pz;
+            const double dx = fma(a.vfx, g.dt, o.xc) - g.px, dy = fma(a.vfy, g.dt, o.yc) - g.py, dz = a.vfz * g.dt - g.pz;
             s_tp[threadIdx.x] = tdbp_pair_tile_prologue(dx, dy, dz, g.ux, g.uy, g.uz, a.off[0], a.off[1]);
         }
         __syncthreads();
         for (int k = 0; k < nb; ++k) {
             const int p = pb + k;
-            const double d_tx = tdbp_pair_tile_dtx(s_tp[k], qx, qy, q2);
-            if (p >= a.first[0] && p < e0) tdbp_pair_tile_pixel(a, a.ch[0], s_tp[k], 0, d_tx, qx, qy, two_inv_ns, p, re0, im0);
-            if (p >= a.first[1] && p < e1) tdbp_pair_tile_pixel(a, a.ch[1], s_tp[k], 1, d_tx, qx, qy, two_inv_ns, p, re1, im1);
+            const double d_tx = tdbp_pair_tile_dtx(s_tp[k], o.qx, o.qy, o.q2);
+            if (p >= a.first[0] && p < e0) tdbp_pair_tile_pixel(a, a.ch[0], s_tp[k], 0, d_tx, o.qx, o.qy, two_inv_ns, p, re0, im0);
+            if (p >= a.first[1] && p < e1) tdbp_pair_tile_pixel(a, a.ch[1], s_tp[k], 1, d_tx, o.qx, o.qy, two_inv_ns, p, re1, im1);
         }
     }
-    if (live) {
-        const size_t n_pix = (size_t)a.nx * a.ny, at = (size_t)blockIdx.y * n_pix + (size_t)iy * a.nx + ix;
+    if (px.live) {
+        const size_t n_pix = (size_t)a.nx * a.ny, at = (size_t)blockIdx.y * n_pix + (size_t)px.iy * a.nx + px.ix;
         a.part[at] = make_double2(re0, im0);
         a.part[(size_t)a.chunks * n_pix + at] = make_double2(re1, im1);
     }
@@ -115,47 +108,31 @@ __global__ __launch_bounds__(256) void tdbp_pair_reduce_kernel(const double2* pa
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_pix) return;
     for (int ch = 0; ch < 2; ++ch) {
-        const double2* src = part + (size_t)ch * chunks * n_pix;
-        double re = 0.0, im = 0.0;
-        for (int c = 0; c < chunks; ++c) {
-            const double2 v = src[(size_t)c * n_pix + i];
-            re += v.x;
-            im += v.y;
-        }
-        if (out128) out128[(size_t)ch * n_pix + i] = make_double2(re, im);
-        if (out64) out64[(size_t)ch * n_pix + i] = make_float2((float)re, (float)im);
+        const double2 z = tdbp_sum_chunks(part + (size_t)ch * chunks * n_pix, chunks, n_pix, i);
+        if (out128) out128[(size_t)ch * n_pix + i] = z;
+        if (out64) out64[(size_t)ch * n_pix + i] = make_float2((float)z.x, (float)z.y);
     }
 }
 
-struct TdbpPair {
-    PairGeo *geo = nullptr, *h_geo = nullptr;              // device table and its page-locked staging
-    hipEvent_t up_done = nullptr;                          // the upload of the last call has read the staging
+struct TdbpPair : TdbpScratch {                            // the table holds PairGeo
     cf* rc1 = nullptr;                                     // [n_p][n_s] range-compressed pulses of channel 1
-    double2* part = nullptr;
-    size_t part_cap = 0;                                   // double2 elements
     float2* raw1 = nullptr;                                // staging of the host entry point
     double2* img128 = nullptr;
     float2* img64 = nullptr;
-    int route = -1;
 };
 
 void tdbp_pair_free(TdbpPair* s) {
     if (!s) return;
-    hipFree(s->geo); hipFree(s->rc1); hipFree(s->part); hipFree(s->raw1); hipFree(s->img128); hipFree(s->img64);
-    if (s->h_geo) hipHostFree(s->h_geo);
-    if (s->up_done) hipEventDestroy(s->up_done);
+    tdbp_scratch_free(s);
+    hipFree(s->rc1); hipFree(s->raw1); hipFree(s->img128); hipFree(s->img64);
     delete s;
 }
-
-#define PCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 static hipError_t pair_scratch(Tdbp* t, TdbpPair** out) {
     if (!t->pair) {
         TdbpPair* s = new TdbpPair();
-        hipError_t e = hipMalloc(&s->geo, (size_t)t->n_p * sizeof(PairGeo));
-        if (e == hipSuccess) e = hipHostMalloc(&s->h_geo, (size_t)t->n_p * sizeof(PairGeo), hipHostMallocDefault);
+        hipError_t e = tdbp_scratch_init(s, t->n_p, sizeof(PairGeo));
         if (e == hipSuccess) e = hipMalloc(&s->rc1, (size_t)t->n_p * t->n_s * sizeof(cf));
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->up_done, hipEventDisableTiming);
         if (e != hipSuccess) { tdbp_pair_free(s); return e; }
         t->pair = s;
     }
@@ -163,20 +140,9 @@ static hipError_t pair_scratch(Tdbp* t, TdbpPair** out) {
     return hipSuccess;
 }
 
-// Nearest and farthest transmit range of one pulse over the pixel rectangle (half side h) moved by v_f dt: the rectangle is convex,
-// so the range is largest at a corner and smallest at the projection of the transmitter clamped to the rectangle.
-static void pair_rect_range(const PulseGeo& g, const double* vf, double h, double* dmin, double* dmax) {
-    const double sx = vf[0] * g.dt, sy = vf[1] * g.dt, gz = vf[2] * g.dt - g.pz;
-    const double qx = g.px - sx, qy = g.py - sy;
-    const double cx = qx < -h ? -h : (qx > h ? h : qx), cy = qy < -h ? -h : (qy > h ? h : qy);
-    *dmin = sqrt((cx - qx) * (cx - qx) + (cy - qy) * (cy - qy) + gz * gz);
-    const double ax = fabs(qx) + h, ay = fabs(qy) + h;
-    *dmax = sqrt(ax * ax + ay * ay + gz * gz);
-}
-
 // Sample window [lo, hi) that either channel can touch over the pulses [u0, u1), whether the series of tdbp_pair_pixel holds, and
 // whether the pair's part of the tile expansion does (the d_tx part is tdbp_tile_ok's).
-// d_tx lies in pair_rect_range; the receiver is |off| from the transmitter, so |d_rx - d_tx| <= |off| (triangle inequality) and
+// d_tx lies in moved_rect_range (tdbp.hip); the receiver is |off| from the transmitter, so |d_rx - d_tx| <= |off| (triangle inequality) and
 // |e| = |d_rx^2 / d_tx^2 - 1| <= 2 |off| / d_tx + (off / d_tx)^2.
 static void pair_bounds(const Tdbp* t, const std::vector<PulseGeo>& geo, int u0, int u1, const double* vf, double t_start, double scene_size,
                         const sarx_tdbp_pair_params* prm, int* lo, int* hi, bool* series, bool* tile) {
@@ -185,12 +151,12 @@ static void pair_bounds(const Tdbp* t, const std::vector<PulseGeo>& geo, int u0,
     double imin = 1e300, imax = -1e300;
     *series = true;
     // the remainder of d_tx - d_rx about a tile's reference pixel (tdbp_pixel.hpp): |q|^2 |off| / (sqrt(3) (d_min - |off|)^2), q the
-    // farthest pixel of a 16 x 16 tile from its reference pixel (index 8 of 16), as tdbp_tile_ok takes it
-    *tile = t->nx >= 2 && t->ny >= 2;
-    const double qm = *tile ? 8.0 * hypot(scene_size / (double)(t->nx - 1), scene_size / (double)(t->ny - 1)) : 0.0;
+    // tile's reach (tdbp_tile_reach), as tdbp_tile_ok takes it
+    const double qm = tdbp_tile_reach(t, scene_size);
+    *tile = qm >= 0.0;
     for (int p = u0; p < u1; ++p) {
         double dmin, dmax;
-        pair_rect_range(geo[p], vf, h, &dmin, &dmax);
+        moved_rect_range(geo[p], vf, h, &dmin, &dmax);
         const double a = ((2.0 * dmin - om) / c - t_start + prm->chirp_centre_s) * fs;
         const double b = ((2.0 * dmax + om) / c - t_start + prm->chirp_centre_s) * fs;
         if (a < imin) imin = a;
@@ -199,17 +165,14 @@ static void pair_bounds(const Tdbp* t, const std::vector<PulseGeo>& geo, int u0,
         if (!(dmin > 0.0) || !(7.0 / 256.0 * e * e * e * e * e * dmax < 1e-9)) *series = false;
         if (!(dmin > om) || !(qm * qm * om / (sqrt(3.0) * (dmin - om) * (dmin - om)) < 1e-9)) *tile = false;
     }
-    // x = idx - 0.5 rounded through float32 (< 1 sample at any n_s <= 2^23), i0 = floor(x), i0 + 1 is read too
-    const double l = floor(imin) - 3.0, u = ceil(imax) + 4.0;
-    *lo = !(l > 0) ? 0 : (l > (double)t->n_s ? t->n_s : (int)l);
-    *hi = !(u > 0) ? 0 : (u > (double)t->n_s ? t->n_s : (int)u);
+    tdbp_clamp_window(imin, imax, t->n_s, lo, hi);
 }
 
 hipError_t tdbp_pair(Tdbp* t, const float2* raw0, const float2* raw1, const double* pos, const double* vel, const double* t_pulses,
                      double t_start, const double* vel_focus, double scene_size, const sarx_tdbp_pair_params* prm, int chunks,
                      double2* d_img128, float2* d_img64, hipStream_t st) {
     TdbpPair* s = nullptr;
-    PCK(pair_scratch(t, &s));
+    TCK(pair_scratch(t, &s));
     const int n_p = t->n_p;
     const int u0 = prm->first_pulse[0] < prm->first_pulse[1] ? prm->first_pulse[0] : prm->first_pulse[1];
     const int u1 = (prm->first_pulse[0] > prm->first_pulse[1] ? prm->first_pulse[0] : prm->first_pulse[1]) + prm->n_used;
@@ -220,50 +183,34 @@ hipError_t tdbp_pair(Tdbp* t, const float2* raw0, const float2* raw1, const doub
     pair_bounds(t, geo, u0, u1, vel_focus, t_start, scene_size, prm, &lo, &hi, &series, &tile);
     tile = tile && tdbp_tile_ok(t, geo, vel_focus, scene_size);   // the d_tx series, and the switch SARX_TDBP_TILE=0
     if (t->full_rc) { lo = 0; hi = t->n_s; }
-    PCK(tdbp_range_compress(t, raw0, lo, hi, st));
-    cf* const rc0 = t->rc;
-    t->rc = s->rc1;                                        // the same launches, the other destination
-    const hipError_t e1 = tdbp_range_compress(t, raw1, lo, hi, st);
-    t->rc = rc0;
-    PCK(e1);
-    PCK(hipEventSynchronize(s->up_done));                  // the previous call's upload has left the staging (at once as a rule)
-    for (int p = 0; p < n_p; ++p) {
-        PairGeo& g = s->h_geo[p];
-        const double vx = vel[3 * p], vy = vel[3 * p + 1], vz = vel[3 * p + 2];
-        const double inv = 1.0 / sqrt(vx * vx + vy * vy + vz * vz);
-        g.px = geo[p].px; g.py = geo[p].py; g.pz = geo[p].pz;
-        g.ux = vx * inv; g.uy = vy * inv; g.uz = vz * inv;
-        g.dt = geo[p].dt; g.pad = 0.0;
-    }
-    PCK(hipMemcpyAsync(s->geo, s->h_geo, (size_t)n_p * sizeof(PairGeo), hipMemcpyHostToDevice, st));
-    PCK(hipEventRecord(s->up_done, st));
-    PCK(tdbp_ensure_axes(t, scene_size, st));
-    // pulse chunks as the focus-velocity search picks them: enough workgroups to fill the device several times over, never fewer
-    // than 32 pulses each; chunks > 0: the caller's number (sarx_tdbp_search_set_chunks)
-    const int tiles = ((t->nx + 15) / 16) * ((t->ny + 15) / 16), n_u = u1 - u0;
-    if (chunks < 1) {
-        chunks = (16384 + tiles - 1) / tiles;
-        if (chunks > n_u / 32) chunks = n_u / 32;
-    }
-    if (chunks > SARX_TDBP_SEARCH_MAX_CHUNKS) chunks = SARX_TDBP_SEARCH_MAX_CHUNKS;
-    if (chunks > n_u) chunks = n_u;
-    if (chunks < 1) chunks = 1;
-    const int per_chunk = (n_u + chunks - 1) / chunks;
-    chunks = (n_u + per_chunk - 1) / per_chunk;
-    const size_t n_pix = (size_t)t->nx * t->ny, need = 2 * (size_t)chunks * n_pix;
-    if (need > s->part_cap) {
-        PCK(hipFree(s->part));                             // waits for the launches that may still read it
-        s->part = nullptr; s->part_cap = 0;
-        PCK(hipMalloc(&s->part, need * sizeof(double2)));
-        s->part_cap = need;
-    }
+    TCK(tdbp_range_compress(t, raw0, t->rc, lo, hi, st));
+    TCK(tdbp_range_compress(t, raw1, s->rc1, lo, hi, st)); // the same launches, the other destination
+    TCK(tdbp_scratch_upload(s, st, [&](void* staging) {
+        PairGeo* h_geo = (PairGeo*)staging;
+        for (int p = 0; p < n_p; ++p) {
+            PairGeo& g = h_geo[p];
+            const double vx = vel[3 * p], vy = vel[3 * p + 1], vz = vel[3 * p + 2];
+            const double inv = 1.0 / sqrt(vx * vx + vy * vy + vz * vz);
+            g.px = geo[p].px; g.py = geo[p].py; g.pz = geo[p].pz;
+            g.ux = vx * inv; g.uy = vy * inv; g.uz = vz * inv;
+            g.dt = geo[p].dt; g.pad = 0.0;
+        }
+        return hipSuccess;
+    }));
+    TCK(tdbp_ensure_axes(t, scene_size, st));
+    // pulse chunks over the union's pulses, one chunk launching tiles workgroups
+    const int tiles = ((t->nx + 15) / 16) * ((t->ny + 15) / 16);
+    int per_chunk = 0;
+    chunks = tdbp_pick_chunks(tiles, 1, u1 - u0, chunks, &per_chunk);
+    const size_t n_pix = (size_t)t->nx * t->ny;
+    TCK(grow(&s->part, &s->part_cap, 2 * (size_t)chunks * n_pix));
     PairArgs a{};
     a.ch[0].rc = t->rc; a.ch[1].rc = s->rc1;
     for (int c = 0; c < 2; ++c) {
         a.ch[c].fc = t->k.fc; a.ch[c].half_w = (float)t->n_s / 2.0f; a.ch[c].n_s = t->n_s;
         a.off[c] = prm->rx_offset_m[c]; a.first[c] = prm->first_pulse[c];
     }
-    a.geo = s->geo; a.xax = t->xax; a.yax = t->yax; a.part = s->part;
+    a.geo = (const PairGeo*)s->geo; a.xax = t->xax; a.yax = t->yax; a.part = s->part;
     a.vfx = vel_focus[0]; a.vfy = vel_focus[1]; a.vfz = vel_focus[2];
     a.inv_c = 1.0 / t->k.c; a.fs = t->k.fs; a.t_start = t_start; a.chirp_centre = prm->chirp_centre_s; a.inv_ns = 1.0 / (double)t->n_s;
     a.n_used = prm->n_used; a.u0 = u0; a.u1 = u1;
@@ -271,7 +218,7 @@ hipError_t tdbp_pair(Tdbp* t, const float2* raw0, const float2* raw1, const doub
     if (tile) hipLaunchKernelGGL(tdbp_pair_tile_kernel, dim3(tiles, chunks), dim3(256), 0, st, a);
     else if (series) hipLaunchKernelGGL(tdbp_pair_kernel<true>, dim3(tiles, chunks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(tdbp_pair_kernel<false>, dim3(tiles, chunks), dim3(256), 0, st, a);
-    PCK(hipGetLastError());
+    TCK(hipGetLastError());
     s->route = tile ? 1 : 0;
     hipLaunchKernelGGL(tdbp_pair_reduce_kernel, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, st, s->part, chunks, n_pix, d_img128, d_img64);
     return hipGetLastError();
@@ -281,11 +228,11 @@ int tdbp_pair_route(const Tdbp* t) { return t->pair ? t->pair->route : -1; }
 
 hipError_t tdbp_pair_staging(Tdbp* t, float2** d_raw1, double2** d_img128, float2** d_img64) {
     TdbpPair* s = nullptr;
-    PCK(pair_scratch(t, &s));
+    TCK(pair_scratch(t, &s));
     const size_t n_pix = (size_t)t->nx * t->ny;
-    if (!s->raw1) PCK(hipMalloc(&s->raw1, (size_t)t->n_p * t->n_s * sizeof(float2)));
-    if (!s->img128) PCK(hipMalloc(&s->img128, 2 * n_pix * sizeof(double2)));
-    if (!s->img64) PCK(hipMalloc(&s->img64, 2 * n_pix * sizeof(float2)));
+    if (!s->raw1) TCK(hipMalloc(&s->raw1, (size_t)t->n_p * t->n_s * sizeof(float2)));
+    if (!s->img128) TCK(hipMalloc(&s->img128, 2 * n_pix * sizeof(double2)));
+    if (!s->img64) TCK(hipMalloc(&s->img64, 2 * n_pix * sizeof(float2)));
     *d_raw1 = s->raw1; *d_img128 = s->img128; *d_img64 = s->img64;
     return hipSuccess;
 }

@@ -1,6 +1,8 @@
-// One pixel and pulse of the time-domain back-projection (sar_batch_sim.py:205-232), stated once for the focus kernels of tdbp.hip
-// and the focus-velocity search kernels of tdbp_search.hip.  A kernel keeps only its tile and pixel coordinates, where the focus
-// velocity v_f and w = v_plat - v_f come from, the batch loop of the tile form and the place of its partial image.
+// One pixel and pulse of the time-domain back-projection (sar_batch_sim.py:205-232), stated once for the focus kernels of tdbp.hip,
+// the focus-velocity search kernels of tdbp_search.hip and the two-receiver kernels of tdbp_pair.hip, with what stands around it in
+// every one of them: the tile and pixel coordinates of a thread (tdbp_pix), a pixel's offset from its tile's reference pixel
+// (tdbp_tile_offsets) and the fixed-order sum of a pixel's chunks (tdbp_sum_chunks).  A kernel keeps only where the focus velocity
+// v_f and w = v_plat - v_f come from, the batch loop of the tile form and the place of its partial image.
 // Every statement groups its operands as the reference parity (1e-4) was measured with: -ffp-contract=on fuses inside a statement
 // only, so splitting or merging one changes bits.
 #pragma once
@@ -9,6 +11,35 @@
 #include "fft_core.hpp"
 
 namespace sarx {
+
+// One thread per pixel, 256 threads on a 16 x 16 pixel tile, tiles row by row along blockIdx.x.  A dead lane (ragged right and
+// bottom tiles) runs the whole pulse loop on pixel 0's coordinates - the barriers of the tile form need it - and stores nothing.
+struct TdbpPix { int tx, ty, ix, iy; bool live; };
+__device__ __forceinline__ TdbpPix tdbp_pix(int nx, int ny) {
+    const int tiles_x = (nx + 15) >> 4;
+    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+    const int ix = tx * 16 + (threadIdx.x & 15), iy = ty * 16 + (threadIdx.x >> 4);
+    return {tx, ty, ix, iy, ix < nx && iy < ny};
+}
+
+// the tile's reference pixel (index 8 of 16, clamped to the grid) and this pixel's offset q from it: exact differences of the axis tables
+struct TdbpTileOffsets { double xc, yc, qx, qy, q2; };
+__device__ __forceinline__ TdbpTileOffsets tdbp_tile_offsets(const double* xax, const double* yax, const TdbpPix& px, int nx, int ny) {
+    const double xc = xax[min(px.tx * 16 + 8, nx - 1)], yc = yax[min(px.ty * 16 + 8, ny - 1)];
+    const double qx = xax[px.live ? px.ix : 0] - xc, qy = yax[px.live ? px.iy : 0] - yc;
+    return {xc, yc, qx, qy, fma(qx, qx, qy * qy)};
+}
+
+// src: [chunks][n_pix] partial images; the sum of pixel i over the chunks, c rising: the same bits on every run
+__device__ __forceinline__ double2 tdbp_sum_chunks(const double2* src, int chunks, size_t n_pix, size_t i) {
+    double re = 0.0, im = 0.0;
+    for (int c = 0; c < chunks; ++c) {
+        const double2 v = src[(size_t)c * n_pix + i];
+        re += v.x;
+        im += v.y;
+    }
+    return make_double2(re, im);
+}
 
 // A: the kernel's argument struct (TdbpArgs, SearchArgs); read here: rc [n_p][n_s], n_s, half_w, inv_c, fc, fs, t_start, k_shift,
 // inv_ns - the fields tdbp_fill_args (tdbp_plan.h) sets.

@@ -40,7 +40,10 @@ struct Tdbp {
     TdbpPair* pair = nullptr;     // scratch of the two-receiver pair (tdbp_pair.hip), likewise
 };
 
-hipError_t tdbp_range_compress(Tdbp* t, const float2* raw, int lo, int hi, hipStream_t st);
+#define TCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+
+// samples [lo, hi) of every pulse of raw, compressed into dst [n_p][n_s]: t->rc, or the pair's buffer for its second channel
+hipError_t tdbp_range_compress(Tdbp* t, const float2* raw, cf* dst, int lo, int hi, hipStream_t st);
 hipError_t tdbp_ensure_axes(Tdbp* t, double scene_size, hipStream_t st);
 // position and dt = t_pulse - mean(t_pulses) of every pulse; then w = v_plat - vf and |w|^2 for one focus velocity
 void tdbp_pulse_table(const Tdbp* t, const double* pos, const double* t_pulses, std::vector<PulseGeo>& geo);
@@ -49,6 +52,33 @@ void tdbp_set_focus(std::vector<PulseGeo>& geo, const double* vel, const double*
 void tdbp_sample_window(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double t_start, double scene_size,
                         int* lo, int* hi);
 bool tdbp_tile_ok(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double scene_size);
+// what those two bounds and the pair's own (pair_bounds) are made of: the transmit range of one pulse over the moved pixel rectangle of half
+// side h, sample indices to a window inside [0, n_s] (NaN-safe), the farthest pixel of a tile from its reference pixel (< 0: grid too thin)
+void moved_rect_range(const PulseGeo& g, const double* vf, double h, double* dmin, double* dmax);
+void tdbp_clamp_window(double imin, double imax, int n_s, int* lo, int* hi);
+double tdbp_tile_reach(const Tdbp* t, double scene_size);
+// pulse chunks of one search or pair call, and the pulses in each; requested < 1: chosen here
+int tdbp_pick_chunks(int tiles, int blocks_per_chunk, int n_pulses, int requested, int* per_chunk);
+
+// What the search and the pair each hold beside the plan, made by their first call: the per-pulse table of their own record type
+// (SearchGeo, PairGeo) with its page-locked staging, the partial images, and the route the last call took.
+struct TdbpScratch {
+    void *geo = nullptr, *h_geo = nullptr;                 // device table and its page-locked staging
+    size_t bytes = 0;                                      // of either
+    hipEvent_t up_done = nullptr;                          // the uploads of the last call have read the staging
+    double2* part = nullptr; size_t part_cap = 0;          // partial images, grown on demand; double2 elements
+    int route = -1;                                        // 1 tile form, 0 exact form, -1 no call yet
+};
+hipError_t tdbp_scratch_init(TdbpScratch* s, int n_p, size_t bytes);   // n_p records of bytes each
+void tdbp_scratch_free(TdbpScratch* s);
+hipError_t grow(double2** buf, size_t* cap, size_t need);              // *buf holds at least need elements; the old content is not kept
+// fill writes the staging once the previous call's uploads have left it (at once as a rule) and enqueues what else it stages; the table follows
+template <class F> hipError_t tdbp_scratch_upload(TdbpScratch* s, hipStream_t st, F fill) {
+    TCK(hipEventSynchronize(s->up_done));
+    TCK(fill(s->h_geo));
+    TCK(hipMemcpyAsync(s->geo, s->h_geo, s->bytes, hipMemcpyHostToDevice, st));
+    return hipEventRecord(s->up_done, st);
+}
 // the kernel arguments that the focus launch (TdbpArgs) and the search launch (SearchArgs) share
 template <class A> void tdbp_fill_args(const Tdbp* t, double t_start, int per_chunk, A& a) {
     a.rc = t->rc; a.xax = t->xax; a.yax = t->yax;

@@ -13,6 +13,7 @@
 //     when a stack is asked for, and folds P = re^2 + im^2 (products and sum rounded one by one, so P is what fp64 NumPy gives)
 //     into s2 = sum P, s4 = sum P^2, the peak and its place: thread t takes pixels t, t + 1024, ... in rising order, then a
 //     binary tree over the 1024 threads in LDS.  No atomics: the same bits on every run, with or without the stack.
+// Pulse chunks: tdbp_pick_chunks (tdbp.hip); pulse table, its staging and the partial images: a TdbpScratch (tdbp_plan.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -43,11 +44,8 @@ struct SearchArgs {
 };
 
 __global__ __launch_bounds__(256) void tdbp_search_kernel(SearchArgs a) {
-    const int tiles_x = (a.nx + 15) >> 4;
-    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const int ix = tx * 16 + (threadIdx.x & 15), iy = ty * 16 + (threadIdx.x >> 4);
-    const bool live = ix < a.nx && iy < a.ny;
-    const double gx0 = a.xax[live ? ix : 0], gy0 = a.yax[live ? iy : 0];
+    const TdbpPix px = tdbp_pix(a.nx, a.ny);
+    const double gx0 = a.xax[px.live ? px.ix : 0], gy0 = a.yax[px.live ? px.iy : 0];
     const double vfx = a.hyps[3 * blockIdx.z], vfy = a.hyps[3 * blockIdx.z + 1], vfz = a.hyps[3 * blockIdx.z + 2];
     const int p0 = blockIdx.y * a.per_chunk, p1 = min(a.n_p, p0 + a.per_chunk);
     double acc_re = 0.0, acc_im = 0.0;
@@ -61,20 +59,15 @@ __global__ __launch_bounds__(256) void tdbp_search_kernel(SearchArgs a) {
         tdbp_exact_pixel(a, dx, dy, dz, wx, wy, wz, w2, p, acc_re, acc_im);
     }
     const size_t n_pix = (size_t)a.nx * a.ny;
-    if (live) a.part[((size_t)blockIdx.z * a.chunks + blockIdx.y) * n_pix + (size_t)iy * a.nx + ix] = make_double2(acc_re, acc_im);
+    if (px.live) a.part[((size_t)blockIdx.z * a.chunks + blockIdx.y) * n_pix + (size_t)px.iy * a.nx + px.ix] = make_double2(acc_re, acc_im);
 }
 
 // tdbp_tile_kernel with the prologue lane forming w of this hypothesis
 __global__ __launch_bounds__(256) void tdbp_search_tile_kernel(SearchArgs a) {
     __shared__ TilePulse s_tp[TP_BATCH];
-    const int tiles_x = (a.nx + 15) >> 4;
-    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const int ix = tx * 16 + (threadIdx.x & 15), iy = ty * 16 + (threadIdx.x >> 4);
-    const bool live = ix < a.nx && iy < a.ny;
-    const double xc = a.xax[min(tx * 16 + 8, a.nx - 1)], yc = a.yax[min(ty * 16 + 8, a.ny - 1)];
-    const double qx = a.xax[live ? ix : 0] - xc, qy = a.yax[live ? iy : 0] - yc;
-    const double q2 = fma(qx, qx, qy * qy);
-    const float qxf = (float)qx, qyf = (float)qy;
+    const TdbpPix px = tdbp_pix(a.nx, a.ny);
+    const TdbpTileOffsets o = tdbp_tile_offsets(a.xax, a.yax, px, a.nx, a.ny);
+    const float qxf = (float)o.qx, qyf = (float)o.qy;
     const double vfx = a.hyps[3 * blockIdx.z], vfy = a.hyps[3 * blockIdx.z + 1], vfz = a.hyps[3 * blockIdx.z + 2];
     const int p0 = blockIdx.y * a.per_chunk, p1 = min(a.n_p, p0 + a.per_chunk);
     const double two_inv_ns = 2.0 * a.inv_ns;
@@ -86,14 +79,14 @@ __global__ __launch_bounds__(256) void tdbp_search_tile_kernel(SearchArgs a) {
             const SearchGeo g = a.geo[pb + threadIdx.x];
             const double wx = g.vx - vfx, wy = g.vy - vfy, wz = g.vz - vfz;
             const double w2 = wx * wx + wy * wy + wz * wz;
-            const double dx = fma(vfx, g.dt, xc) - g.px, dy = fma(vfy, g.dt, yc) - g.py, dz = vfz * g.dt - g.pz;
+            const double dx = fma(vfx, g.dt, o.xc) - g.px, dy = fma(vfy, g.dt, o.yc) - g.py, dz = vfz * g.dt - g.pz;
             s_tp[threadIdx.x] = tdbp_tile_prologue(a, dx, dy, dz, wx, wy, wz, w2);
         }
         __syncthreads();
-        for (int k = 0; k < nb; ++k) tdbp_tile_pixel(a, s_tp[k], qx, qy, q2, qxf, qyf, two_inv_ns, pb + k, acc_re, acc_im);
+        for (int k = 0; k < nb; ++k) tdbp_tile_pixel(a, s_tp[k], o.qx, o.qy, o.q2, qxf, qyf, two_inv_ns, pb + k, acc_re, acc_im);
     }
     const size_t n_pix = (size_t)a.nx * a.ny;
-    if (live) a.part[((size_t)blockIdx.z * a.chunks + blockIdx.y) * n_pix + (size_t)iy * a.nx + ix] = make_double2(acc_re, acc_im);
+    if (px.live) a.part[((size_t)blockIdx.z * a.chunks + blockIdx.y) * n_pix + (size_t)px.iy * a.nx + px.ix] = make_double2(acc_re, acc_im);
 }
 
 static constexpr int MT = 1024;
@@ -110,6 +103,7 @@ __global__ __launch_bounds__(MT) void tdbp_search_metric_kernel(const double2* p
     double s2 = 0.0, s4 = 0.0, pk = -1.0;
     unsigned long long at = NO_PIXEL;
     for (size_t i = t; i < n_pix; i += MT) {
+        // tdbp_sum_chunks, kept in place: called from here it costs two vector instructions (profiles/r18_tdbp_host_resource_usage.txt)
         double re = 0.0, im = 0.0;
         for (int c = 0; c < chunks; ++c) {
             const double2 v = src[(size_t)c * n_pix + i];
@@ -148,50 +142,31 @@ __global__ __launch_bounds__(MT) void tdbp_search_metric_kernel(const double2* p
     }
 }
 
-struct TdbpSearch {
-    SearchGeo *geo = nullptr, *h_geo = nullptr;            // device table and its page-locked staging
-    double *hyps = nullptr, *h_hyps = nullptr;             // [MAX_HYP][3]
-    hipEvent_t up_done = nullptr;                          // the uploads of the last call have read the staging
-    double2* part = nullptr;
-    size_t part_cap = 0;                                   // double2 elements
+struct TdbpSearch : TdbpScratch {                          // the table holds SearchGeo
+    double *hyps = nullptr, *h_hyps = nullptr;             // [MAX_HYP][3], staged and uploaded with the table
     sarx_tdbp_search_record* rec = nullptr;                // staging of the host entry point
     double2* stack = nullptr;
     size_t stack_cap = 0;
-    int route = -1;
 };
 
 void tdbp_search_free(TdbpSearch* s) {
     if (!s) return;
-    hipFree(s->geo); hipFree(s->hyps); hipFree(s->part); hipFree(s->rec); hipFree(s->stack);
-    if (s->h_geo) hipHostFree(s->h_geo);
+    tdbp_scratch_free(s);
+    hipFree(s->hyps); hipFree(s->rec); hipFree(s->stack);
     if (s->h_hyps) hipHostFree(s->h_hyps);
-    if (s->up_done) hipEventDestroy(s->up_done);
     delete s;
 }
-
-#define SCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 static hipError_t search_scratch(Tdbp* t, TdbpSearch** out) {
     if (!t->search) {
         TdbpSearch* s = new TdbpSearch();
-        hipError_t e = hipMalloc(&s->geo, (size_t)t->n_p * sizeof(SearchGeo));
-        if (e == hipSuccess) e = hipHostMalloc(&s->h_geo, (size_t)t->n_p * sizeof(SearchGeo), hipHostMallocDefault);
+        hipError_t e = tdbp_scratch_init(s, t->n_p, sizeof(SearchGeo));
         if (e == hipSuccess) e = hipMalloc(&s->hyps, (size_t)SARX_TDBP_SEARCH_MAX_HYP * 3 * sizeof(double));
         if (e == hipSuccess) e = hipHostMalloc(&s->h_hyps, (size_t)SARX_TDBP_SEARCH_MAX_HYP * 3 * sizeof(double), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->up_done, hipEventDisableTiming);
         if (e != hipSuccess) { tdbp_search_free(s); return e; }
         t->search = s;
     }
     *out = t->search;
-    return hipSuccess;
-}
-
-static hipError_t grow(double2** buf, size_t* cap, size_t need) {
-    if (need <= *cap) return hipSuccess;
-    SCK(hipFree(*buf));                                    // waits for the launches that may still read it
-    *buf = nullptr; *cap = 0;
-    SCK(hipMalloc(buf, need * sizeof(double2)));
-    *cap = need;
     return hipSuccess;
 }
 
@@ -205,7 +180,7 @@ hipError_t tdbp_search(Tdbp* t, const float2* raw, const double* pos, const doub
                        const double* vel_hyps, int n_hyp, double scene_size, int chunks, double2* d_images,
                        sarx_tdbp_search_record* d_records, hipStream_t st) {
     TdbpSearch* s = nullptr;
-    SCK(search_scratch(t, &s));
+    TCK(search_scratch(t, &s));
     const int n_p = t->n_p;
     // window and route: the bound and the tile condition of the focus, evaluated for every hypothesis
     std::vector<PulseGeo> geo;
@@ -220,40 +195,31 @@ hipError_t tdbp_search(Tdbp* t, const float2* raw, const double* pos, const doub
         if (u > l) { if (l < lo) lo = l; if (u > hi) hi = u; }
         if (tile) tile = tdbp_tile_ok(t, geo, vf, scene_size);
     }
-    SCK(tdbp_range_compress(t, raw, lo, hi, st));
-    SCK(hipEventSynchronize(s->up_done));                  // the previous call's uploads have left the staging (at once as a rule)
-    for (int p = 0; p < n_p; ++p) {
-        SearchGeo& g = s->h_geo[p];
-        g.px = geo[p].px; g.py = geo[p].py; g.pz = geo[p].pz;
-        g.vx = vel[3 * p]; g.vy = vel[3 * p + 1]; g.vz = vel[3 * p + 2];
-        g.dt = geo[p].dt; g.pad = 0.0;
-    }
-    memcpy(s->h_hyps, vel_hyps, (size_t)n_hyp * 3 * sizeof(double));
-    SCK(hipMemcpyAsync(s->geo, s->h_geo, (size_t)n_p * sizeof(SearchGeo), hipMemcpyHostToDevice, st));
-    SCK(hipMemcpyAsync(s->hyps, s->h_hyps, (size_t)n_hyp * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    SCK(hipEventRecord(s->up_done, st));
-    SCK(tdbp_ensure_axes(t, scene_size, st));
-    // pulse chunks: enough workgroups to fill the device several times over, never fewer than 32 pulses each; fewer chunks with
-    // more hypotheses, so the partial images stay near 16384 workgroups x 4 KiB
+    TCK(tdbp_range_compress(t, raw, t->rc, lo, hi, st));
+    TCK(tdbp_scratch_upload(s, st, [&](void* staging) {
+        SearchGeo* h_geo = (SearchGeo*)staging;
+        for (int p = 0; p < n_p; ++p) {
+            SearchGeo& g = h_geo[p];
+            g.px = geo[p].px; g.py = geo[p].py; g.pz = geo[p].pz;
+            g.vx = vel[3 * p]; g.vy = vel[3 * p + 1]; g.vz = vel[3 * p + 2];
+            g.dt = geo[p].dt; g.pad = 0.0;
+        }
+        memcpy(s->h_hyps, vel_hyps, (size_t)n_hyp * 3 * sizeof(double));
+        return hipMemcpyAsync(s->hyps, s->h_hyps, (size_t)n_hyp * 3 * sizeof(double), hipMemcpyHostToDevice, st);
+    }));
+    TCK(tdbp_ensure_axes(t, scene_size, st));
+    // a chunk launches tiles x n_hyp workgroups: fewer chunks with more hypotheses, the partial images stay near 16384 workgroups x 4 KiB
     const int tiles = ((t->nx + 15) / 16) * ((t->ny + 15) / 16);
-    if (chunks < 1) {
-        const long long blocks = (long long)tiles * n_hyp;
-        chunks = (int)((16384 + blocks - 1) / blocks);
-        if (chunks > n_p / 32) chunks = n_p / 32;
-    }
-    if (chunks > SARX_TDBP_SEARCH_MAX_CHUNKS) chunks = SARX_TDBP_SEARCH_MAX_CHUNKS;
-    if (chunks > n_p) chunks = n_p;
-    if (chunks < 1) chunks = 1;
-    const int per_chunk = (n_p + chunks - 1) / chunks;
-    chunks = (n_p + per_chunk - 1) / per_chunk;
-    SCK(grow(&s->part, &s->part_cap, (size_t)n_hyp * chunks * t->nx * t->ny));
+    int per_chunk = 0;
+    chunks = tdbp_pick_chunks(tiles, n_hyp, n_p, chunks, &per_chunk);
+    TCK(grow(&s->part, &s->part_cap, (size_t)n_hyp * chunks * t->nx * t->ny));
     SearchArgs a{};
     tdbp_fill_args(t, t_start, per_chunk, a);
-    a.geo = s->geo; a.hyps = s->hyps; a.part = s->part; a.chunks = chunks;
+    a.geo = (const SearchGeo*)s->geo; a.hyps = s->hyps; a.part = s->part; a.chunks = chunks;
     const dim3 grid(tiles, chunks, n_hyp);
     if (tile) hipLaunchKernelGGL(tdbp_search_tile_kernel, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(tdbp_search_kernel, grid, dim3(256), 0, st, a);
-    SCK(hipGetLastError());
+    TCK(hipGetLastError());
     s->route = tile ? 1 : 0;
     return launch_metric(t, s->part, chunks, n_hyp, d_images, d_records, st);
 }
@@ -266,12 +232,12 @@ int tdbp_search_route(const Tdbp* t) { return t->search ? t->search->route : -1;
 
 hipError_t tdbp_search_staging(Tdbp* t, int n_hyp, bool images, sarx_tdbp_search_record** d_records, double2** d_images, hipStream_t st) {
     TdbpSearch* s = nullptr;
-    SCK(search_scratch(t, &s));
-    if (!s->rec) SCK(hipMalloc(&s->rec, (size_t)SARX_TDBP_SEARCH_MAX_HYP * sizeof(sarx_tdbp_search_record)));
+    TCK(search_scratch(t, &s));
+    if (!s->rec) TCK(hipMalloc(&s->rec, (size_t)SARX_TDBP_SEARCH_MAX_HYP * sizeof(sarx_tdbp_search_record)));
     *d_records = s->rec;
     *d_images = nullptr;
     if (images) {
-        SCK(grow(&s->stack, &s->stack_cap, (size_t)n_hyp * t->nx * t->ny));
+        TCK(grow(&s->stack, &s->stack_cap, (size_t)n_hyp * t->nx * t->ny));
         *d_images = s->stack;
     }
     return hipSuccess;

@@ -95,6 +95,22 @@ def test_tile_route_against_the_restatement_and_the_exact_route(native, shift):
     assert max(ref.rel_l2(one.img1, res.img1), ref.rel_l2(one.img2, res.img2)) < 1e-12
 
 
+def test_more_chunks_asked_for_than_the_union_has_pulses():
+    """The stationary scene on 33 x 17 pixels (ragged tiles in both directions), channel 0 on pulses [3, 48) and channel 1 on
+    [0, 45): a union of 48 pulses and chunks=64, so the chunk picker stops at one pulse per chunk, 48 chunks, and at either end
+    of the union three chunks hold a pulse of one channel only."""
+    sc = ref.stationary_scene()
+    first, n_used = (3, 0), 45
+    want = ref.pair_images(sc["raw"], sc["pos"], sc["vel"], sc["t_vec"], sc["t_start"], sc["num_samples"], 400.0, 33, 17, sc["k"],
+                           sc["rx_offsets"], sc["chirp_centre"], first, n_used, rc=sc.get("rc"))   # the compressed pulses, if an earlier test left them
+    res = _pair(sc, 400.0, 33, 17, (first, n_used), chunks=64)
+    print(f"route {res.route}")
+    for c, img in enumerate((res.img1, res.img2)):
+        err = ref.rel_l2(img, want[c])
+        print(f"channel {c}: rel L2 {err:.2e}")
+        assert err < TOL, c
+
+
 def test_tile_route_with_a_focus_velocity(native):
     sc, _ = native
     vf = (2.0, 6.0, 0.0)
