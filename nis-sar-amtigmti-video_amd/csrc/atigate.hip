@@ -14,10 +14,12 @@
 //                thread in rising e, then across the lanes in a butterfly (lane ^ 32, 16, ... 1: an IEEE sum does not depend on
 //                the order of its two operands, so all lanes hold the same bits), then across the four waves in wave order
 //                through LDS.  Thread 0 derives coh, psi, sigma and the decision and writes the record and the keep flag.
-//   compaction : one workgroup of 1024 threads ranks the keep flags with ballot / mbcnt prefix sums, 1024 reports a round, as
+//   compaction : one workgroup of 1024 threads ranks the keep flags with gmti_dev.hpp's block_rank, 1024 reports a round, as
 //                cluster.hip ranks its plots, copies the kept reports as six 8-byte words each and fills in out_index.
 // No global atomics, no scratch, the same bytes in every run.
 #include "atigate.h"
+
+#include "gmti_dev.hpp"
 
 // every fp64 operation rounds on its own: the sums are sums of exact products, thr = k_sigma * sigma is one rounded product
 #pragma clang fp contract(off)
@@ -30,15 +32,12 @@ constexpr int AG_SUMS = 6;                          // c11, c22, c12_re, c12_im,
 constexpr int AGC_THREADS = 1024;
 constexpr int AGC_WAVES = AGC_THREADS / 64;
 
-__device__ __forceinline__ int ag_extent(int x, int h, int n) { return min(x + h, n - 1) - max(x - h, 0) + 1; }
-
 template <int K> __global__ __launch_bounds__(AG_THREADS) void atigate_stats_kernel(AtiGateArgs g) {
     __shared__ double part[AG_WAVES][AG_SUMS];
-    const sarx_gmti_header* hin = reinterpret_cast<const sarx_gmti_header*>(g.in);
-    const uint32_t count = hin->count;
-    if (hin->overflow != 0 || count > (uint32_t)g.p.max_detections || blockIdx.x >= count) return;      // workgroup-uniform
+    const SlotView in = slot_view(g.in, g.p.max_detections);
+    if (in.unusable || blockIdx.x >= in.count) return;         // workgroup-uniform
     const int r = blockIdx.x, tid = threadIdx.x;
-    const int2 ij = *reinterpret_cast<const int2*>(reinterpret_cast<const sarx_gmti_report*>(hin + 1) + r);   // i and j lead the record
+    const int2 ij = *reinterpret_cast<const int2*>(in.rep + r);         // i and j lead the record
     const bool valid = (unsigned)ij.x < (unsigned)g.n_az && (unsigned)ij.y < (unsigned)g.n_rg;
     const int i = valid ? ij.x : 0, j = valid ? ij.y : 0;
     const int ga = g.p.guard_az, gr = g.p.guard_rg, oa = ga + g.p.train_az, orr = gr + g.p.train_rg;
@@ -104,8 +103,8 @@ template <int K> __global__ __launch_bounds__(AG_THREADS) void atigate_stats_ker
     sarx_atigate_stat st{};
     st.c11 = s[0]; st.c22 = s[1]; st.c12_re = s[2]; st.c12_im = s[3]; st.i_re = s[4]; st.i_im = s[5];
     if (valid) {
-        st.n_train = ag_extent(i, oa, g.n_az) * ag_extent(j, orr, g.n_rg) - ag_extent(i, ga, g.n_az) * ag_extent(j, gr, g.n_rg);
-        st.n_look = ag_extent(i, la, g.n_az) * ag_extent(j, lr, g.n_rg);
+        st.n_train = train_count(i, j, ga, gr, oa, orr, g.n_az, g.n_rg);
+        st.n_look = box_extent(i, la, g.n_az) * box_extent(j, lr, g.n_rg);
     }
     const double prod = s[0] * s[1];
     if (st.n_train < g.p.min_train) {
@@ -134,48 +133,23 @@ template <int K> __global__ __launch_bounds__(AG_THREADS) void atigate_stats_ker
     if (g.stats) g.stats[r] = st;
 }
 
-// rank of this thread among the flagged threads of the workgroup (thread order) and their number
-__device__ inline int atigate_rank(bool flag, int& total, int* wsum) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    const int within = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-    if (lane == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int w = 0; w < AGC_WAVES; ++w) {
-        const int c = wsum[w];
-        tot += c;
-        if (w < wave) before += c;
-    }
-    __syncthreads();
-    total = tot;
-    return before + within;
-}
-
 __global__ __launch_bounds__(AGC_THREADS) void atigate_compact_kernel(AtiGateArgs g) {
     __shared__ int wsum[AGC_WAVES];
     const int tid = threadIdx.x;
-    const sarx_gmti_header* hin = reinterpret_cast<const sarx_gmti_header*>(g.in);
-    sarx_gmti_header* hout = reinterpret_cast<sarx_gmti_header*>(g.out);
-    const uint32_t count = hin->count;
-    if (hin->overflow != 0 || count > (uint32_t)g.p.max_detections) {
-        if (tid == 0) {
-            sarx_gmti_header h{};
-            h.count = count;
-            h.overflow = 1u;
-            *hout = h;
-        }
+    const SlotView in = slot_view(g.in, g.p.max_detections);
+    if (in.unusable) {
+        if (tid == 0) slot_close(g.out, in.count, true);
         return;
     }
-    const int n = (int)count;
-    const uint64_t* src = reinterpret_cast<const uint64_t*>(hin + 1);        // a report is six 8-byte words
-    uint64_t* dst = reinterpret_cast<uint64_t*>(hout + 1);
+    const int n = (int)in.count;
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(in.rep);         // a report is six 8-byte words
+    uint64_t* dst = reinterpret_cast<uint64_t*>(slot_reports(g.out));
     int done = 0;
     for (int base = 0; base < n; base += AGC_THREADS) {
         const int r = base + tid;
         const bool kept = r < n && g.keep[r] != 0;
         int total;
-        const int k = done + atigate_rank(kept, total, wsum);
+        const int k = done + block_rank<AGC_WAVES>(kept, total, wsum);
         done += total;
         if (kept) {
             uint64_t w[6];
@@ -186,11 +160,7 @@ __global__ __launch_bounds__(AGC_THREADS) void atigate_compact_kernel(AtiGateArg
             if (g.stats) g.stats[r].out_index = k;
         }
     }
-    if (tid == 0) {
-        sarx_gmti_header h{};
-        h.count = (uint32_t)done;
-        *hout = h;
-    }
+    if (tid == 0) slot_close(g.out, (uint32_t)done, false);
 }
 
 template <int K> static void launch_stats(const AtiGateArgs& a, hipStream_t st) {

@@ -12,12 +12,14 @@
 //   keys     : (i, j) are staged in LDS when the capacity is at most 4096 reports (32 KiB); above that they are read from the slot
 //              itself (at most 768 KiB, L2-resident).
 //   order    : the keys (label << 14 | index) are sorted in LDS (bitonic): components become contiguous, members in rising index.
-//   plots    : the thread at the start of a component walks it for the peak; ballot / mbcnt prefix sums over the peak flags in
-//              report order give the plot ranks; the thread that owns the peak's index then walks the component again and forms
+//   plots    : the thread at the start of a component walks it for the peak; gmti_dev.hpp's block_rank over the peak flags in
+//              report order gives the plot ranks; the thread that owns the peak's index then walks the component again and forms
 //              every fp64 value alone, one addition after another.  No global atomics, no scratch, the same bits in every run.
 // LDS: 2 x 4 x pow2ceil(capacity) bytes (+ 8 x capacity for the keys): 64 KiB at 4096, 128 KiB at 16384 reports, above the 64 KiB
 // a launch gets without asking, hence hipFuncAttributeMaxDynamicSharedMemorySize.
 #include "cluster.h"
+
+#include "gmti_dev.hpp"
 
 // the sums must be the restatement's: every fp64 operation rounds on its own
 #pragma clang fp contract(off)
@@ -69,24 +71,6 @@ __device__ inline int least_linked_label(const sarx_gmti_report* rep, const int2
     return m;
 }
 
-// rank of this thread among the flagged threads of the workgroup (thread order) and their number
-__device__ inline int cluster_rank(bool flag, int& total, int* wsum) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    const int within = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-    if (lane == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int w = 0; w < CLUSTER_WAVES; ++w) {
-        const int c = wsum[w];
-        tot += c;
-        if (w < wave) before += c;
-    }
-    __syncthreads();
-    total = tot;
-    return before + within;
-}
-
 // sixteen waves are four per SIMD: the register budget is that of four, not of the eight the compiler would aim for (it spilt)
 template <bool LK>
 __global__ __launch_bounds__(CLUSTER_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void cluster_kernel(ClusterArgs a, int pcap) {
@@ -97,27 +81,20 @@ __global__ __launch_bounds__(CLUSTER_THREADS) __attribute__((amdgpu_waves_per_eu
     int2* keys = reinterpret_cast<int2*>(cur + 2 * (size_t)pcap);      // [max_detections] when LK
     const int tid = threadIdx.x, md = a.p.max_detections;
     const size_t f = blockIdx.x;
-    const sarx_gmti_header* hin = reinterpret_cast<const sarx_gmti_header*>(a.in + f * a.in_stride);
-    const sarx_gmti_report* rep = reinterpret_cast<const sarx_gmti_report*>(hin + 1);
-    sarx_gmti_header* hout = reinterpret_cast<sarx_gmti_header*>(a.out + f * a.out_stride);
-    sarx_gmti_report* out = reinterpret_cast<sarx_gmti_report*>(hout + 1);
+    const SlotView in = slot_view(a.in + f * a.in_stride, md);
+    const sarx_gmti_report* rep = in.rep;
+    char* out_slot = a.out + f * a.out_stride;
+    sarx_gmti_report* out = slot_reports(out_slot);
     sarx_cluster_plot* plots = a.plots ? reinterpret_cast<sarx_cluster_plot*>(a.plots + f * a.plots_stride) : nullptr;
     int32_t* labels = a.labels ? a.labels + f * (size_t)md : nullptr;
 
-    const uint32_t count = hin->count;
-    const bool slot_bad = hin->overflow != 0 || count > (uint32_t)md;
     if (labels)
         for (int r = tid; r < md; r += CLUSTER_THREADS) labels[r] = -1;
-    if (slot_bad || count == 0) {
-        if (tid == 0) {
-            sarx_gmti_header h{};
-            h.count = count;
-            h.overflow = slot_bad ? 1u : 0u;
-            *hout = h;
-        }
+    if (in.unusable || in.count == 0) {
+        if (tid == 0) slot_close(out_slot, in.count, in.unusable);
         return;
     }
-    const int n = (int)count;
+    const int n = (int)in.count;
     const int az = a.p.link_az, rg = a.p.link_rg;
 
     for (int r = tid; r < n; r += CLUSTER_THREADS) {
@@ -201,7 +178,7 @@ __global__ __launch_bounds__(CLUSTER_THREADS) __attribute__((amdgpu_waves_per_eu
         const int r = base + tid;
         const bool is_peak = r < n && mark[r] != 0;
         int total;
-        const int k = done + cluster_rank(is_peak, total, wsum);
+        const int k = done + block_rank<CLUSTER_WAVES>(is_peak, total, wsum);
         done += total;
         if (!is_peak) continue;
         const int start = mark[r] - 1, label = srt[start] >> INDEX_BITS;
@@ -238,11 +215,7 @@ __global__ __launch_bounds__(CLUSTER_THREADS) __attribute__((amdgpu_waves_per_eu
         out[k] = zp;
         if (plots) plots[k] = pl;
     }
-    if (tid == 0) {
-        sarx_gmti_header h{};
-        h.count = (uint32_t)done;
-        *hout = h;
-    }
+    if (tid == 0) slot_close(out_slot, (uint32_t)done, false);
 }
 
 static int pow2ceil(int n) {

@@ -27,6 +27,8 @@
 // order.  No atomics.
 #include "coherence.h"
 
+#include "gmti_dev.hpp"
+
 namespace sarx {
 
 typedef float2 cf;
@@ -56,8 +58,6 @@ template <bool SUB> __device__ __forceinline__ void coh_cell(cf a, cf b, bool ok
     const unsigned nz = ((ax != 0.0 || ay != 0.0) ? 1u : 0u) + ((bx != 0.0 || by != 0.0) ? 0x10000u : 0u);
     s.n = SUB ? s.n - nz : s.n + nz;
 }
-
-__device__ __forceinline__ int coh_extent(int x, int h, int n) { return min(x + h, n - 1) - max(x - h, 0) + 1; }
 
 template <bool IG, bool CH> __global__ __launch_bounds__(COH_THREADS) void coherence_kernel(CoherenceArgs p) {
     __shared__ double V[4][COH_R][COH_THREADS];
@@ -132,7 +132,7 @@ template <bool IG, bool CH> __global__ __launch_bounds__(COH_THREADS) void coher
             for (int q = 0; q < 4; ++q) t[q] += V[q][hrow][lc0 + d];
             tn += VN[hrow][lc0 + d];
         }
-        const int rows_n = coh_extent(min(gi, n_az - 1), ha, n_az);
+        const int rows_n = box_extent(min(gi, n_az - 1), ha, n_az);
 #pragma unroll
         for (int k = 0; k < COH_SEG; ++k) {
             const int lc = lc0 + k;
@@ -159,7 +159,7 @@ template <bool IG, bool CH> __global__ __launch_bounds__(COH_THREADS) void coher
                 p.coh[idx] = coh;
                 if (IG) p.igram[idx] = make_float2((float)g_re, (float)g_im);
                 if (CH) {
-                    const double need = p.power_floor * (double)(rows_n * coh_extent(gj, hr, n_rg));
+                    const double need = p.power_floor * (double)(rows_n * box_extent(gj, hr, n_rg));
                     const bool tested = s11 >= need && s22 >= need;
                     const bool changed = tested && coh < p.threshold;
                     if (p.mask) p.mask[idx] = changed ? 2 : (tested ? 1 : 0);

@@ -1,9 +1,9 @@
 // GMTI detection on the DPCA magnitude plane (include/sarx_gmti.h): a cell-averaging CFAR launch that appends the peaks of the
 // detected cells to a list, and a refine launch that sorts the list by (i, j) and adds the ATI interferogram of each report.
 //
-// CFAR: one workgroup per TH x TW tile.  The tile and a halo of HA rows / HR columns (the outer half-widths rounded up to 8, 16 or
-// 32) are read into LDS with range-direction (contiguous) loads, all issued before the first wait; outside the image the tile
-// holds zeros, so every box sum below is a sum over the cells inside the image.  Box sums of P = m^2 are separable and fp64
+// CFAR: one workgroup per tile of gmti_dev.hpp, which states the tile's geometry, the peak rule, the report and the ranks for
+// this detector and for oscfar.hip.  The tile and its halo are read into LDS with range-direction (contiguous) loads,
+// all issued before the first wait; outside the image the tile holds zeros.  Box sums of P = m^2 are separable and fp64
 // throughout: a vertical pass writes per column the sums over the outer and the guard rows of each output row (running sums over
 // eight output rows per thread), a horizontal pass slides the same two windows along each row.  The training sum is outer - guard:
 // in fp64 the error of that difference is about 1e-16 of the largest P in the window, far inside the threshold's resolution even
@@ -14,21 +14,20 @@
 
 #include <climits>
 
+#include "gmti_dev.hpp"
+
 namespace sarx {
 
-static constexpr int GM_TH = 32, GM_TW = 64, GM_THREADS = 256;
 static constexpr int GM_SEG = 8;              // output rows (vertical pass) / columns (horizontal pass) per running sum
+static constexpr int REFINE_THREADS = 256;
 
-__device__ __forceinline__ int box_extent(int x, int h, int n) { return min(x + h, n - 1) - max(x - h, 0) + 1; }
-
-template <int HA, int HR> __global__ __launch_bounds__(GM_THREADS) void gmti_cfar_kernel(GmtiCfarArgs a) {
-    constexpr int LH = GM_TH + 2 * HA, LW = GM_TW + 2 * HR;
+template <int HA, int HR> __global__ __launch_bounds__(CFAR_THREADS) void gmti_cfar_kernel(GmtiCfarArgs a) {
+    using Tile = CfarTile<HA, HR>;
+    constexpr int LH = Tile::LH, LW = Tile::LW, K = Tile::K;
     constexpr int VW = LW + 1;                // odd row stride (doubles): the horizontal pass reads one column of 32 rows per half-wave
-    constexpr int K = LH * LW / GM_THREADS;
-    static_assert(LH * LW % GM_THREADS == 0, "tile fill: whole loads per thread");
     __shared__ float tile[LH][LW];
-    __shared__ double vo[GM_TH][VW], vg[GM_TH][VW];
-    const int r0 = blockIdx.y * GM_TH, c0 = blockIdx.x * GM_TW;
+    __shared__ double vo[CFAR_TH][VW], vg[CFAR_TH][VW];
+    const int r0 = blockIdx.y * CFAR_TH, c0 = blockIdx.x * CFAR_TW;
     const int tid = threadIdx.x;
 
     // tile fill: every address is clamped into the image (always a valid load), the value outside it is replaced by zero afterwards,
@@ -36,14 +35,14 @@ template <int HA, int HR> __global__ __launch_bounds__(GM_THREADS) void gmti_cfa
     float v[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int e = tid + k * GM_THREADS;
+        const int e = tid + k * CFAR_THREADS;
         const int gr = r0 - HA + e / LW, gc = c0 - HR + e % LW;
         const int cr = min(max(gr, 0), a.n_az - 1), cc = min(max(gc, 0), a.n_rg - 1);
         v[k] = a.m[(size_t)cr * a.n_rg + cc];
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int e = tid + k * GM_THREADS;
+        const int e = tid + k * CFAR_THREADS;
         const int gr = r0 - HA + e / LW, gc = c0 - HR + e % LW;
         const bool inside = (unsigned)gr < (unsigned)a.n_az && (unsigned)gc < (unsigned)a.n_rg;
         tile[e / LW][e % LW] = inside ? v[k] : 0.f;
@@ -51,7 +50,7 @@ template <int HA, int HR> __global__ __launch_bounds__(GM_THREADS) void gmti_cfa
     __syncthreads();
 
     // vertical pass: column c of the tile, output rows [seg * 8, seg * 8 + 8)
-    for (int item = tid; item < (GM_TH / GM_SEG) * LW; item += GM_THREADS) {
+    for (int item = tid; item < (CFAR_TH / GM_SEG) * LW; item += CFAR_THREADS) {
         const int c = item % LW, rb = (item / LW) * GM_SEG;
         const int lr = rb + HA;                                   // tile row of output row rb
         double so = 0.0, sg = 0.0;
@@ -72,13 +71,12 @@ template <int HA, int HR> __global__ __launch_bounds__(GM_THREADS) void gmti_cfa
     __syncthreads();
 
     // horizontal pass: output row r, output columns [cb, cb + 8); threshold and peak rule per cell
-    const int r = tid & (GM_TH - 1), cb = (tid / GM_TH) * GM_SEG;
+    const int r = tid & (CFAR_TH - 1), cb = (tid / CFAR_TH) * GM_SEG;
     const int gi = r0 + r;
     const int lr = r + HA;
     double so = 0.0, sg = 0.0;
     for (int d = -a.orr; d <= a.orr; ++d) so += vo[r][HR + cb + d];
     for (int d = -a.gr; d <= a.gr; ++d) sg += vg[r][HR + cb + d];
-    const int rows_o = box_extent(gi, a.oa, a.n_az), rows_g = box_extent(gi, a.ga, a.n_az);
     unsigned det = 0;
     double pw[GM_SEG], mn[GM_SEG];
 #pragma unroll
@@ -89,21 +87,14 @@ template <int HA, int HR> __global__ __launch_bounds__(GM_THREADS) void gmti_cfa
             sg += vg[r][lc + a.gr]; sg -= vg[r][lc - 1 - a.gr];
         }
         const int gj = c0 + cb + q;
-        const int n_train = rows_o * box_extent(gj, a.orr, a.n_rg) - rows_g * box_extent(gj, a.gr, a.n_rg);
+        const int n_train = train_count(gi, gj, a.ga, a.gr, a.oa, a.orr, a.n_az, a.n_rg);
         const float mc = tile[lr][lc];
         const double p = (double)mc * (double)mc;
         const double mean = fmax(so - sg, 0.0) / (double)max(n_train, 1);
         pw[q] = p;
         mn[q] = mean;
-        bool hit = gi < a.n_az && gj < a.n_rg && n_train >= a.min_train && p > 0.0 && p > a.alpha * mean;
-        if (hit) {                                                // peak rule: the maximum of the guard box, ties to the smaller index
-            for (int di = -a.ga; di <= a.ga && hit; ++di)
-                for (int dj = -a.gr; dj <= a.gr; ++dj) {
-                    if (!di && !dj) continue;
-                    const float mq = tile[lr + di][lc + dj];      // zero outside the image: never above mc > 0
-                    if (mq > mc || (mq == mc && (di < 0 || (di == 0 && dj < 0)))) { hit = false; break; }
-                }
-        }
+        const bool hit = gi < a.n_az && gj < a.n_rg && n_train >= a.min_train && p > 0.0 && p > a.alpha * mean &&
+                         guard_box_peak<LW>(tile, lr, lc, mc, a.ga, a.gr);
         det |= (unsigned)hit << q;
     }
 
@@ -113,9 +104,9 @@ template <int HA, int HR> __global__ __launch_bounds__(GM_THREADS) void gmti_cfa
     unsigned total = 0;
 #pragma unroll
     for (int q = 0; q < GM_SEG; ++q) {
-        const unsigned long long b = __ballot((det >> q) & 1u);
-        off[q] = total + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        total += (unsigned)__popcll(b);
+        unsigned hits;
+        off[q] = total + lane_rank((det >> q) & 1u, hits);
+        total += hits;
     }
     if (total == 0) return;                                       // wave-uniform
     unsigned base = 0;
@@ -127,50 +118,27 @@ template <int HA, int HR> __global__ __launch_bounds__(GM_THREADS) void gmti_cfa
 #pragma unroll
     for (int q = 0; q < GM_SEG; ++q) {
         const unsigned slot = base + off[q];
-        if (((det >> q) & 1u) && slot < (unsigned)a.max_det) {
-            sarx_gmti_report* o = a.rep + slot;
-            o->i = gi;
-            o->j = c0 + cb + q;
-            o->power = pw[q];
-            o->mean = mn[q];
-            o->interf_re = 0.0;
-            o->interf_im = 0.0;
-            o->mag1 = 0.f;
-            o->mag2 = 0.f;
-        }
+        if (((det >> q) & 1u) && slot < (unsigned)a.max_det) store_bare_report(a.rep + slot, gi, c0 + cb + q, pw[q], mn[q]);
     }
 }
 
-template <int HA, int HR> static void launch_cfar_tpl(const GmtiCfarArgs& a, hipStream_t st) {
-    const dim3 grid((a.n_rg + GM_TW - 1) / GM_TW, (a.n_az + GM_TH - 1) / GM_TH);
-    hipLaunchKernelGGL((gmti_cfar_kernel<HA, HR>), grid, dim3(GM_THREADS), 0, st, a);
-}
-template <int HA> static void launch_cfar_rg(const GmtiCfarArgs& a, hipStream_t st) {
-    if (a.orr <= 8) launch_cfar_tpl<HA, 8>(a, st);
-    else if (a.orr <= 16) launch_cfar_tpl<HA, 16>(a, st);
-    else launch_cfar_tpl<HA, 32>(a, st);
-}
-
 hipError_t launch_gmti_cfar(const GmtiCfarArgs& a, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(a.hdr, 0, sizeof(sarx_gmti_header), st);
-    if (e != hipSuccess) return e;
-    if (a.oa <= 8) launch_cfar_rg<8>(a, st);
-    else if (a.oa <= 16) launch_cfar_rg<16>(a, st);
-    else launch_cfar_rg<32>(a, st);
-    return hipGetLastError();
+    return launch_cfar_tiles(a.hdr, a.n_az, a.n_rg, a.oa, a.orr, st, [&](auto ha, auto hr, dim3 grid) {
+        hipLaunchKernelGGL((gmti_cfar_kernel<ha(), hr()>), grid, dim3(CFAR_THREADS), 0, st, a);
+    });
 }
 
 // Refine: one thread per report.  Its rank in (i, j) order is the number of smaller keys in the list (keys staged through LDS,
 // 256 at a time), so the sorted list does not depend on the order in which the CFAR waves appended.  The interferogram is summed
 // in fp64 over the 3 x 3 neighbourhood clipped to the image.
-__global__ __launch_bounds__(GM_THREADS) void gmti_refine_kernel(const float2* __restrict__ s1, const float2* __restrict__ s2, int n_az,
+__global__ __launch_bounds__(REFINE_THREADS) void gmti_refine_kernel(const float2* __restrict__ s1, const float2* __restrict__ s2, int n_az,
                                                                 int n_rg, double cc, double cs, const sarx_gmti_report* __restrict__ src,
                                                                 sarx_gmti_report* __restrict__ dst, const sarx_gmti_header* hdr,
                                                                 int max_det) {
-    __shared__ long long keys[GM_THREADS];
+    __shared__ long long keys[REFINE_THREADS];
     const int n = (int)min(hdr->count, (unsigned)max_det);
-    if ((int)(blockIdx.x * GM_THREADS) >= n) return;              // workgroup-uniform
-    const int t = blockIdx.x * GM_THREADS + threadIdx.x;
+    if ((int)(blockIdx.x * REFINE_THREADS) >= n) return;              // workgroup-uniform
+    const int t = blockIdx.x * REFINE_THREADS + threadIdx.x;
     sarx_gmti_report rep{};
     long long mine = LLONG_MAX;
     if (t < n) {
@@ -178,12 +146,12 @@ __global__ __launch_bounds__(GM_THREADS) void gmti_refine_kernel(const float2* _
         mine = (long long)rep.i * n_rg + rep.j;
     }
     int rank = 0;
-    for (int b = 0; b < n; b += GM_THREADS) {
+    for (int b = 0; b < n; b += REFINE_THREADS) {
         __syncthreads();
         const int k = b + threadIdx.x;
         keys[threadIdx.x] = k < n ? (long long)src[k].i * n_rg + src[k].j : LLONG_MAX;
         __syncthreads();
-        const int lim = min(GM_THREADS, n - b);
+        const int lim = min(REFINE_THREADS, n - b);
         for (int q = 0; q < lim; ++q) rank += keys[q] < mine;
     }
     if (t >= n) return;
@@ -212,8 +180,8 @@ __global__ __launch_bounds__(GM_THREADS) void gmti_refine_kernel(const float2* _
 
 hipError_t launch_gmti_refine(const float2* s1, const float2* s2, int n_az, int n_rg, double cal_phase, const sarx_gmti_report* src,
                               sarx_gmti_report* dst, const sarx_gmti_header* hdr, int max_det, hipStream_t st) {
-    const int blocks = (max_det + GM_THREADS - 1) / GM_THREADS;
-    hipLaunchKernelGGL(gmti_refine_kernel, dim3(blocks), dim3(GM_THREADS), 0, st, s1, s2, n_az, n_rg, cos(cal_phase), sin(cal_phase),
+    const int blocks = (max_det + REFINE_THREADS - 1) / REFINE_THREADS;
+    hipLaunchKernelGGL(gmti_refine_kernel, dim3(blocks), dim3(REFINE_THREADS), 0, st, s1, s2, n_az, n_rg, cos(cal_phase), sin(cal_phase),
                        src, dst, hdr, max_det);
     return hipGetLastError();
 }

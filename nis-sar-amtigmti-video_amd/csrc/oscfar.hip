@@ -1,8 +1,9 @@
 // Ordered-statistic CFAR on the DPCA magnitude plane (include/sarx_oscfar.h): the launch that stands where gmti.hip's CA launch
 // stands and appends to the same list; the refine launch of gmti.hip sorts it.
 //
-// One workgroup per TH x TW tile.  The tile and its halo are read into LDS as the CA kernel reads them (clamped addresses, every
-// load issued before the first wait, zeros outside the image).  The order in which the rules are applied is the reverse of the CA
+// One workgroup per tile of gmti_dev.hpp, which states the tile's geometry, the peak rule, the report and the ranks for both
+// detectors; the tile and its halo are read into LDS as the CA kernel reads them (clamped addresses, every load issued before
+// the first wait, zeros outside the image).  The order in which the rules are applied is the reverse of the CA
 // kernel's, because here the threshold is the expensive one:
 //   1. peak rule, every cell: a cell inside the image with P > 0, N >= min_train that is the maximum of its guard box is a
 //      candidate.  Candidates are compacted into an LDS list (ballot + mbcnt prefix, one LDS atomic per wave and pass); the list
@@ -18,19 +19,30 @@
 // exact in fp64: there is no multiply-add to contract and nothing to reassociate in these expressions.
 #include "oscfar.h"
 
+#include "gmti_dev.hpp"
+
 namespace sarx {
 
-static constexpr int OS_TH = 32, OS_TW = 64, OS_THREADS = 256, OS_WAVES = OS_THREADS / 64;
-static constexpr int OS_CELLS = OS_TH * OS_TW;
-static constexpr int OS_PER_THREAD = OS_CELLS / OS_THREADS;
+static constexpr int OS_WAVES = CFAR_THREADS / 64;
+static constexpr int OS_CELLS = CFAR_TH * CFAR_TW;
+static constexpr int OS_PER_THREAD = OS_CELLS / CFAR_THREADS;
 static constexpr unsigned short OS_DETECTED = 0x8000;             // flag on a candidate's tile index (< OS_CELLS = 2048)
-
-__device__ __forceinline__ int os_extent(int x, int h, int n) { return min(x + h, n - 1) - max(x - h, 0) + 1; }
 
 struct OsCell {
     int lr, lc;                  // tile coordinates of the cell under test
     int gi, gj;                  // image coordinates
+    int k;                       // the rank scaled to the cell's training count: the k-th smallest is its level
 };
+
+// the candidate with tile index `cell` of the tile at (r0, c0)
+template <int HA, int HR> __device__ __forceinline__ OsCell os_cell(const OsCfarArgs& args, int r0, int c0, int cell) {
+    const GmtiCfarArgs& a = args.base;
+    OsCell c;
+    c.lr = cell / CFAR_TW + HA; c.lc = cell % CFAR_TW + HR; c.gi = r0 + cell / CFAR_TW; c.gj = c0 + cell % CFAR_TW;
+    const int n_train = train_count(c.gi, c.gj, a.ga, a.gr, a.oa, a.orr, a.n_az, a.n_rg);
+    c.k = (args.rank * n_train + args.n_full - 1) / args.n_full;
+    return c;
+}
 
 // Whether at least `need` training cells of `c` satisfy pred(m_t).  Wave-uniform: every lane returns the same answer.
 template <int LW, class Pred>
@@ -55,22 +67,21 @@ __device__ __forceinline__ bool os_count_reaches(const float (*tile)[LW], const 
     return cnt >= need;
 }
 
-template <int HA, int HR> __global__ __launch_bounds__(OS_THREADS) void gmti_oscfar_kernel(OsCfarArgs args) {
-    constexpr int LH = OS_TH + 2 * HA, LW = OS_TW + 2 * HR;
-    constexpr int K = LH * LW / OS_THREADS;
-    static_assert(LH * LW % OS_THREADS == 0, "tile fill: whole loads per thread");
+template <int HA, int HR> __global__ __launch_bounds__(CFAR_THREADS) void gmti_oscfar_kernel(OsCfarArgs args) {
+    using Tile = CfarTile<HA, HR>;
+    constexpr int LH = Tile::LH, LW = Tile::LW, K = Tile::K;
     __shared__ float tile[LH][LW];
     __shared__ unsigned short cand[OS_CELLS];
     __shared__ unsigned n_cand;
     const GmtiCfarArgs& a = args.base;
-    const int r0 = blockIdx.y * OS_TH, c0 = blockIdx.x * OS_TW;
+    const int r0 = blockIdx.y * CFAR_TH, c0 = blockIdx.x * CFAR_TW;
     const int tid = threadIdx.x, lane = tid & 63;
 
     // tile fill, as in gmti.hip: clamped addresses (always a valid load), zero outside the image afterwards
     float v[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int e = tid + k * OS_THREADS;
+        const int e = tid + k * CFAR_THREADS;
         const int gr = r0 - HA + e / LW, gc = c0 - HR + e % LW;
         const int cr = min(max(gr, 0), a.n_az - 1), cc = min(max(gc, 0), a.n_rg - 1);
         v[k] = a.m[(size_t)cr * a.n_rg + cc];
@@ -78,7 +89,7 @@ template <int HA, int HR> __global__ __launch_bounds__(OS_THREADS) void gmti_osc
     __builtin_amdgcn_sched_barrier(0);                            // every load is issued before the first is waited for
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int e = tid + k * OS_THREADS;
+        const int e = tid + k * CFAR_THREADS;
         const int gr = r0 - HA + e / LW, gc = c0 - HR + e % LW;
         const bool inside = (unsigned)gr < (unsigned)a.n_az && (unsigned)gc < (unsigned)a.n_rg;
         tile[e / LW][e % LW] = inside ? v[k] : 0.f;
@@ -89,26 +100,20 @@ template <int HA, int HR> __global__ __launch_bounds__(OS_THREADS) void gmti_osc
     // 1. candidates: a wave takes one tile row of 64 cells per pass (consecutive LDS addresses)
 #pragma unroll 1
     for (int q = 0; q < OS_PER_THREAD; ++q) {
-        const int e = tid + q * OS_THREADS;
-        const int r = e / OS_TW, c = e % OS_TW;
+        const int e = tid + q * CFAR_THREADS;
+        const int r = e / CFAR_TW, c = e % CFAR_TW;
         const int gi = r0 + r, gj = c0 + c, lr = r + HA, lc = c + HR;
         const float mc = tile[lr][lc];
-        const int n_train = os_extent(gi, a.oa, a.n_az) * os_extent(gj, a.orr, a.n_rg) - os_extent(gi, a.ga, a.n_az) * os_extent(gj, a.gr, a.n_rg);
+        const int n_train = train_count(gi, gj, a.ga, a.gr, a.oa, a.orr, a.n_az, a.n_rg);
         bool is = gi < a.n_az && gj < a.n_rg && n_train >= a.min_train && (double)mc * (double)mc > 0.0;
-        if (is) {                                                 // peak rule: the maximum of the guard box, ties to the smaller index
-            for (int di = -a.ga; di <= a.ga && is; ++di)
-                for (int dj = -a.gr; dj <= a.gr; ++dj) {
-                    if (!di && !dj) continue;
-                    const float mq = tile[lr + di][lc + dj];      // zero outside the image: never above mc > 0
-                    if (mq > mc || (mq == mc && (di < 0 || (di == 0 && dj < 0)))) { is = false; break; }
-                }
-        }
-        const unsigned long long b = __ballot(is);
-        if (b == 0) continue;                                     // wave-uniform
+        if (is) is = guard_box_peak<LW>(tile, lr, lc, mc, a.ga, a.gr);      // a branch, not one && chain: mc stays loaded before the tests
+        unsigned found;
+        const unsigned within = lane_rank(is, found);
+        if (found == 0) continue;                                 // wave-uniform
         unsigned base = 0;
-        if (lane == 0) base = atomicAdd(&n_cand, (unsigned)__popcll(b));
+        if (lane == 0) base = atomicAdd(&n_cand, found);
         base = __shfl(base, 0);
-        if (is) cand[base + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u))] = (unsigned short)e;
+        if (is) cand[base + within] = (unsigned short)e;
     }
     __syncthreads();
 
@@ -118,13 +123,10 @@ template <int HA, int HR> __global__ __launch_bounds__(OS_THREADS) void gmti_osc
     unsigned mine = 0;
     for (int idx = wave; idx < nc; idx += OS_WAVES) {
         const int e = cand[idx];
-        OsCell c;
-        c.lr = e / OS_TW + HA; c.lc = e % OS_TW + HR; c.gi = r0 + e / OS_TW; c.gj = c0 + e % OS_TW;
-        const int n_train = os_extent(c.gi, a.oa, a.n_az) * os_extent(c.gj, a.orr, a.n_rg) - os_extent(c.gi, a.ga, a.n_az) * os_extent(c.gj, a.gr, a.n_rg);
-        const int k = (args.rank * n_train + args.n_full - 1) / args.n_full;
+        const OsCell c = os_cell<HA, HR>(args, r0, c0, e);
         const float mc = tile[c.lr][c.lc];
         const double p = (double)mc * (double)mc, alpha = a.alpha;
-        if (os_count_reaches<LW>(tile, a, c, lane, k, [=](float x) { return alpha * ((double)x * (double)x) < p; })) {
+        if (os_count_reaches<LW>(tile, a, c, lane, c.k, [=](float x) { return alpha * ((double)x * (double)x) < p; })) {
             cand[idx] = (unsigned short)(e | OS_DETECTED);
             ++mine;
         }
@@ -142,49 +144,25 @@ template <int HA, int HR> __global__ __launch_bounds__(OS_THREADS) void gmti_osc
         const int e = cand[idx];
         if (!(e & OS_DETECTED)) continue;                         // wave-uniform
         if (slot >= (unsigned)a.max_det) return;                  // overflowed: the list is an error, nothing more to write
-        const int cell = e & (OS_CELLS - 1);
-        OsCell c;
-        c.lr = cell / OS_TW + HA; c.lc = cell % OS_TW + HR; c.gi = r0 + cell / OS_TW; c.gj = c0 + cell % OS_TW;
-        const int n_train = os_extent(c.gi, a.oa, a.n_az) * os_extent(c.gj, a.orr, a.n_rg) - os_extent(c.gi, a.ga, a.n_az) * os_extent(c.gj, a.gr, a.n_rg);
-        const int k = (args.rank * n_train + args.n_full - 1) / args.n_full;
+        const OsCell c = os_cell<HA, HR>(args, r0, c0, e & (OS_CELLS - 1));
         unsigned bits = 0;                                        // the smallest v with #{|m_t| <= v} >= k is the k-th smallest |m_t|
         for (int b = 30; b >= 0; --b) {
             const unsigned trial = bits | ((1u << b) - 1u);
-            if (!os_count_reaches<LW>(tile, a, c, lane, k, [=](float x) { return (__float_as_uint(x) & 0x7fffffffu) <= trial; })) bits |= 1u << b;
+            if (!os_count_reaches<LW>(tile, a, c, lane, c.k, [=](float x) { return (__float_as_uint(x) & 0x7fffffffu) <= trial; })) bits |= 1u << b;
         }
         if (lane == 0) {
             const float mc = tile[c.lr][c.lc], mk = __uint_as_float(bits);
-            sarx_gmti_report* o = a.rep + slot;
-            o->i = c.gi;
-            o->j = c.gj;
-            o->power = (double)mc * (double)mc;
-            o->mean = (double)mk * (double)mk;
-            o->interf_re = 0.0;
-            o->interf_im = 0.0;
-            o->mag1 = 0.f;
-            o->mag2 = 0.f;
+            store_bare_report(a.rep + slot, c.gi, c.gj, (double)mc * (double)mc, (double)mk * (double)mk);
         }
         ++slot;
     }
 }
 
-template <int HA, int HR> static void launch_oscfar_tpl(const OsCfarArgs& a, hipStream_t st) {
-    const dim3 grid((a.base.n_rg + OS_TW - 1) / OS_TW, (a.base.n_az + OS_TH - 1) / OS_TH);
-    hipLaunchKernelGGL((gmti_oscfar_kernel<HA, HR>), grid, dim3(OS_THREADS), 0, st, a);
-}
-template <int HA> static void launch_oscfar_rg(const OsCfarArgs& a, hipStream_t st) {
-    if (a.base.orr <= 8) launch_oscfar_tpl<HA, 8>(a, st);
-    else if (a.base.orr <= 16) launch_oscfar_tpl<HA, 16>(a, st);
-    else launch_oscfar_tpl<HA, 32>(a, st);
-}
-
 hipError_t launch_gmti_oscfar(const OsCfarArgs& a, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(a.base.hdr, 0, sizeof(sarx_gmti_header), st);
-    if (e != hipSuccess) return e;
-    if (a.base.oa <= 8) launch_oscfar_rg<8>(a, st);
-    else if (a.base.oa <= 16) launch_oscfar_rg<16>(a, st);
-    else launch_oscfar_rg<32>(a, st);
-    return hipGetLastError();
+    const GmtiCfarArgs& b = a.base;
+    return launch_cfar_tiles(b.hdr, b.n_az, b.n_rg, b.oa, b.orr, st, [&](auto ha, auto hr, dim3 grid) {
+        hipLaunchKernelGGL((gmti_oscfar_kernel<ha(), hr()>), grid, dim3(CFAR_THREADS), 0, st, a);
+    });
 }
 
 }  // namespace sarx

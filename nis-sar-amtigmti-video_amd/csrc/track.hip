@@ -7,10 +7,12 @@
 //                          reports each over the predicted positions of the live tracks.  The grid is sized by the capacities;
 //                          counts come from the device headers and workgroups without work leave at once.
 //   track_resolve_kernel : one workgroup of 1024 threads: matches, updates, status, drops, then the free slots and the births in
-//                          order, paired through ballot / popcount prefix sums.  No atomics anywhere: every sum is an integer
+//                          order, paired through gmti_dev.hpp's block_rank.  No atomics anywhere: every sum is an integer
 //                          count formed in a fixed order, every fp64 value is computed by exactly one thread.
 // Both searches form d2 with the same operations on the same operands, so the two sides agree on every pair bit for bit.
 #include "track.h"
+
+#include "gmti_dev.hpp"
 
 // the decisions must be the restatement's: every fp64 operation rounds on its own
 #pragma clang fp contract(off)
@@ -37,9 +39,9 @@ __device__ inline double pair_d2(double di, double dj, double ga, double gr) {
 __global__ __launch_bounds__(PAIR_THREADS) void track_pair_kernel(TrackArgs a, int n_tb) {
     __shared__ double2 sh[PAIR_CHUNK];
     if (a.hdr->error != SARX_TRACK_OK) return;
-    const uint32_t count = a.slot_hdr->count;
-    if (a.slot_hdr->overflow != 0 || count > (uint32_t)a.p.max_detections) return;
-    const int n = (int)count, tid = threadIdx.x;
+    const SlotView in = slot_view(a.slot_hdr, a.p.max_detections);      // count and unusable only: the reports come as a.rep
+    if (in.unusable) return;
+    const int n = (int)in.count, tid = threadIdx.x;
     const double ga = a.p.gate_az, gr = a.p.gate_rg, sa = gate_slack(ga), sr = gate_slack(gr);
     if ((int)blockIdx.x < n_tb) {
         // ---- tracks over reports ----
@@ -106,24 +108,6 @@ __global__ __launch_bounds__(PAIR_THREADS) void track_pair_kernel(TrackArgs a, i
     if (active) a.best_t[r] = best;
 }
 
-// rank of this thread among the flagged threads of the workgroup (thread order) and their number
-__device__ inline int block_rank(bool flag, int& total, int* wsum) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    const int within = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-    if (lane == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int w = 0; w < RESOLVE_WAVES; ++w) {
-        const int c = wsum[w];
-        tot += c;
-        if (w < wave) before += c;
-    }
-    __syncthreads();
-    total = tot;
-    return before + within;
-}
-
 __device__ inline int block_sum(int v, int* wsum) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
@@ -142,9 +126,8 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void track_resolve_kernel(TrackArg
     __shared__ int wsum[RESOLVE_WAVES];
     const int tid = threadIdx.x;
     const sarx_track_header h0 = *a.hdr;
-    const uint32_t count = a.slot_hdr->count;
-    const bool slot_bad = a.slot_hdr->overflow != 0 || count > (uint32_t)a.p.max_detections;
-    if (h0.error != SARX_TRACK_OK || slot_bad) {
+    const SlotView in = slot_view(a.slot_hdr, a.p.max_detections);
+    if (h0.error != SARX_TRACK_OK || in.unusable) {
         if (a.assoc)
             for (int r = tid; r < a.p.max_detections; r += RESOLVE_THREADS) a.assoc[r] = -1;
         if (h0.error == SARX_TRACK_OK && tid == 0) {
@@ -153,7 +136,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void track_resolve_kernel(TrackArg
         }
         return;
     }
-    const int n = (int)count;
+    const int n = (int)in.count;
     const bool have_live = h0.n_live != 0;        // without a live track the pair kernel wrote no best_t: every report is unheld
 
     // the assoc row as "nobody", and how many reports would start a track
@@ -217,7 +200,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void track_resolve_kernel(TrackArg
             const int t = base + tid;
             const bool is_free = t < a.p.max_tracks && a.slots[t].status == SARX_TRACK_FREE;
             int total;
-            const int k = done + block_rank(is_free, total, wsum);
+            const int k = done + block_rank<RESOLVE_WAVES>(is_free, total, wsum);
             if (is_free && k < births) a.free_slot[k] = t;
             done += total;
         }
@@ -229,7 +212,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void track_resolve_kernel(TrackArg
             const int r = base + tid;
             const bool born = r < n && (!have_live || a.best_t[r] < 0) && may_start(a.rep[r], a.p.birth_ratio);
             int total;
-            const int k = done + block_rank(born, total, wsum);
+            const int k = done + block_rank<RESOLVE_WAVES>(born, total, wsum);
             done += total;
             if (!born) continue;
             const sarx_gmti_report z = a.rep[r];

@@ -1,5 +1,6 @@
 """GMTI detection on the GPU (sarx.gmti_detect, focus_ati_dpca(detect=...), TwoChannelBatch(stack="detections")) against the NumPy
 restatement of its semantics (tests/_gmti_numpy.py), on synthetic planes and on the C3 scene."""
+import functools
 import os
 import socket
 import subprocess
@@ -45,11 +46,9 @@ CASES = [((64, 64), (2, 2), (8, 8), 1e-3, 0.0),
          ((4096, 4096), (2, 2), (8, 8), 1e-5, 0.0)]
 
 
-@pytest.mark.parametrize("shape,guard,train,pfa,cal", CASES, ids=[f"{c[0][0]}x{c[0][1]}-g{c[1]}-t{c[2]}" for c in CASES])
-def test_parity_on_synthetic_planes(shape, guard, train, pfa, cal):
+def _assert_parity(m, s1, s2, guard, train, pfa, cal):
     import sarx
-    n_az, n_rg = shape
-    m, s1, s2 = _synthetic(n_az, n_rg, seed=n_az + 7 * n_rg + guard[1])
+    n_az, n_rg = m.shape
     ra, ca = 5e5 + 0.25 * np.arange(n_rg), 1.2 * (np.arange(n_az) - n_az / 2)
     rep = sarx.gmti_detect(s1.T, s2.T, ra, ca, wavelength_m=LAM, platform_speed_mps=V, lag_s=LAG, guard=guard, train=train, pfa=pfa,
                            cal_phase=cal, max_detections=65536, dpca_mag=m.T)
@@ -75,6 +74,33 @@ def test_parity_on_synthetic_planes(shape, guard, train, pfa, cal):
     np.testing.assert_allclose(d["v_los_mps"], -LAM * np.angle(want) / (4 * np.pi * LAG), atol=1e-4)
     np.testing.assert_allclose(d["cross_range_relocated_m"], ca[ii] + ra[jj] * d["v_los_mps"] / V, rtol=1e-12)
     assert rep.v_ambiguity_mps == pytest.approx(LAM / (4 * LAG))
+
+
+@pytest.mark.parametrize("shape,guard,train,pfa,cal", CASES, ids=[f"{c[0][0]}x{c[0][1]}-g{c[1]}-t{c[2]}" for c in CASES])
+def test_parity_on_synthetic_planes(shape, guard, train, pfa, cal):
+    n_az, n_rg = shape
+    _assert_parity(*_synthetic(n_az, n_rg, seed=n_az + 7 * n_rg + guard[1]), guard, train, pfa, cal)
+
+
+LADDER = (8, 9, 16, 17)                   # outer half-widths at the steps of the halo ladder: HA, HR = 8, 16, 16, 32
+LADDER_GUARD = (2, 2)
+
+
+@functools.lru_cache(maxsize=None)
+def _ladder_plane():
+    planes = _synthetic(96, 80, seed=96 + 7 * 80)                 # past one tile in both directions
+    for x in planes:
+        x.setflags(write=False)
+    return planes
+
+
+@pytest.mark.parametrize("outer_rg", LADDER)
+@pytest.mark.parametrize("outer_az", LADDER)
+def test_parity_on_every_rung_of_the_halo_ladder(outer_az, outer_rg):
+    """The sixteen windows reach all nine (HA, HR) instantiations of the CFAR kernel; _assert_parity holds every case to a
+    non-empty reference list."""
+    train = (outer_az - LADDER_GUARD[0], outer_rg - LADDER_GUARD[1])
+    _assert_parity(*_ladder_plane(), LADDER_GUARD, train, 1e-3, 0.4)
 
 
 def test_determinism_and_overflow():

@@ -100,6 +100,27 @@ def test_bit_identical_to_the_restatement(shape, guard, train, rank_name):
             assert len(o["cells"]) >= 1
 
 
+LADDER = (8, 9, 16, 17)                   # outer half-widths at the steps of the halo ladder: HA, HR = 8, 16, 16, 32
+LADDER_GUARD = (2, 2)
+
+
+@pytest.mark.parametrize("outer_rg", LADDER)
+@pytest.mark.parametrize("outer_az", LADDER)
+def test_bit_identical_on_every_rung_of_the_halo_ladder(outer_az, outer_rg):
+    """The sixteen windows reach all nine (HA, HR) instantiations of the OS kernel, on the plane that is past one tile in both
+    directions, at the default rank."""
+    from sarx.gmti import os_cfar_alpha
+    train = (outer_az - LADDER_GUARD[0], outer_rg - LADDER_GUARD[1])
+    nf, rank = ref.n_full(LADDER_GUARD, train), ref.default_rank(LADDER_GUARD, train)
+    m = _plane((96, 80))
+    rep = _detect(m, guard=LADDER_GUARD, train=train, pfa=PFA)
+    assert (rep.method, rep.rank, rep.n_full) == ("os", rank, nf)
+    assert rep.alpha == os_cfar_alpha(PFA, nf, rank)
+    o = ref.oscfar(m, LADDER_GUARD, train, alpha=rep.alpha, rank=rep.rank)
+    assert len(o["cells"]) >= 1                                           # a case cannot pass by detecting nothing
+    _assert_identical(rep, o)
+
+
 @pytest.mark.parametrize("shape,guard,train", [((1, 200), (0, 5), (0, 12)), ((200, 1), (4, 0), (9, 0)), ((33, 65), (2, 2), (8, 8))],
                          ids=["1x200", "200x1", "33x65"])
 def test_thin_planes_and_borders_with_min_train_one(shape, guard, train):
