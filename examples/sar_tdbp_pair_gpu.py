@@ -6,9 +6,11 @@ on the device on the orbit arc of sar_batch_sim.py:262-268 (along track = x), ba
 and handed to the ATI / DPCA launch as they lie.  The C3 scene (a grid of stationary scatterers, a 15 m/s and a 2 m/s radial
 mover) is turned onto that orbit (ground range = y) and moved along track so that the fast mover, which its radial speed
 displaces by v_los R0 / V_ground, is imaged at the middle of the chip.  Prints the DPCA peak, its ATI phase and the radial speed
-it gives against the geometry's.
+it gives against the geometry's.  With --search the pair goes through sarx.gmti_detect, and the strongest reports go back to the
+pulses: sarx.tdbp_pair_search images a small chip around each under a line of along-track focus velocities and prints, per report,
+the along-track speed of the sharpest DPCA difference and the radial speed at the refocused peak.
 
-    python3 examples/sar_tdbp_pair_gpu.py [--pulses 512] [--chip 256] [--scene-size 360] [--out pair.npz]"""
+    python3 examples/sar_tdbp_pair_gpu.py [--pulses 512] [--chip 256] [--scene-size 360] [--out pair.npz] [--search]"""
 import argparse
 import os
 import sys
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--chip", type=int, default=256)
     ap.add_argument("--scene-size", type=float, default=360.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--search", action="store_true", help="detect on the pair and search each report's along-track focus velocity")
     a = ap.parse_args()
     import sarx
     from sarx import radar
@@ -64,9 +67,29 @@ def main():
     if a.out:
         np.savez(a.out, img1=res.img1.numpy(), img2=res.img2.numpy(), x_axis=axis, y_axis=axis, lag_s=res.lag_s,
                  **{k: prod[k] for k in ("ati_phase", "ati_phase_masked", "slc1_mag", "dpca_mag")})
+    if a.search:
+        search(sarx, a, res, raws, pos, vel, offs, t_start, n_s, t_vec, consts, axis, speed)
     res.release()
     for r in raws:
         r.release()
+
+
+def search(sarx, a, res, raws, pos, vel, offs, t_start, n_s, t_vec, consts, axis, speed, most=8, half_span=24.0, n_hyp=9):
+    """pair -> gmti_detect -> tdbp_pair_search on the strongest reports, a line of n_hyp along-track focus velocities."""
+    from sarx import slot
+    rep = sarx.gmti_detect(res.img1, res.img2, axis, axis, wavelength_m=consts["C"] / consts["FC"], platform_speed_mps=speed, lag_s=res.lag_s)
+    d = rep.detections[np.argsort(-rep.detections["power"])[:most]]
+    print(f"{len(rep)} reports; the search takes the {len(d)} strongest")
+    if not len(d):
+        return
+    reports = np.zeros(len(d), slot.REPORT_DTYPE)
+    reports["i"], reports["j"] = d["i"], d["j"]
+    hyps = sarx.tdbp_velocity_line((0.0, 0.0, 0.0), (1.0, 0.0, 0.0), half_span, n_hyp)       # along track = x on this orbit
+    out = sarx.tdbp_pair_search(raws[0], raws[1], pos, vel, offs, t_start, n_s, t_vec, a.scene_size, a.chip, a.chip, reports, hyps,
+                                chip=(32, 32), consts=consts)
+    for r, (est, v_los) in enumerate(zip(out.estimate(), out.v_los())):
+        print(f"report at ({axis[d['j'][r]]:.1f}, {axis[d['i'][r]]:.1f}) m: along track {est.velocity[0]:+.1f} m/s{' (end of the line)' if est.edge else ''}, "
+              f"v_los {v_los:+.2f} m/s at ({axis[out.peak_ix[r]]:.1f}, {axis[out.peak_iy[r]]:.1f}) m")
 
 
 if __name__ == "__main__":

@@ -108,6 +108,7 @@ void tdbp_destroy(Tdbp* t) {
     hipFree(t->part); hipFree(t->img);
     tdbp_search_free(t->search);
     tdbp_pair_free(t->pair);
+    tdbp_pair_search_free(t->pair_search);
     delete t;
 }
 

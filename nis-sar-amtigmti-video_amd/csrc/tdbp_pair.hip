@@ -27,12 +27,6 @@ namespace sarx {
 
 static_assert(sizeof(sarx_tdbp_pair_params) == 40, "sarx_tdbp_pair_params is 40 bytes");
 
-struct PairGeo {             // one 64-byte record per pulse
-    double px, py, pz;       // transmitter
-    double ux, uy, uz;       // v^ = vel_tx / |vel_tx|
-    double dt, pad;
-};
-
 struct PairArgs {
     PairChan ch[2];
     const PairGeo* geo;
@@ -144,8 +138,8 @@ static hipError_t pair_scratch(Tdbp* t, TdbpPair** out) {
 // whether the pair's part of the tile expansion does (the d_tx part is tdbp_tile_ok's).
 // d_tx lies in moved_rect_range (tdbp.hip); the receiver is |off| from the transmitter, so |d_rx - d_tx| <= |off| (triangle inequality) and
 // |e| = |d_rx^2 / d_tx^2 - 1| <= 2 |off| / d_tx + (off / d_tx)^2.
-static void pair_bounds(const Tdbp* t, const std::vector<PulseGeo>& geo, int u0, int u1, const double* vf, double t_start, double scene_size,
-                        const sarx_tdbp_pair_params* prm, int* lo, int* hi, bool* series, bool* tile) {
+void tdbp_pair_bounds(const Tdbp* t, const std::vector<PulseGeo>& geo, int u0, int u1, const double* vf, double t_start, double scene_size,
+                      const sarx_tdbp_pair_params* prm, int* lo, int* hi, bool* series, bool* tile) {
     const double c = t->k.c, fs = t->k.fs, h = scene_size / 2;
     const double om = fmax(fabs(prm->rx_offset_m[0]), fabs(prm->rx_offset_m[1]));
     double imin = 1e300, imax = -1e300;
@@ -168,6 +162,24 @@ static void pair_bounds(const Tdbp* t, const std::vector<PulseGeo>& geo, int u0,
     tdbp_clamp_window(imin, imax, t->n_s, lo, hi);
 }
 
+void tdbp_pair_table(PairGeo* h_geo, const std::vector<PulseGeo>& geo, const double* vel, int n_p) {
+    for (int p = 0; p < n_p; ++p) {
+        PairGeo& g = h_geo[p];
+        const double vx = vel[3 * p], vy = vel[3 * p + 1], vz = vel[3 * p + 2];
+        const double inv = 1.0 / sqrt(vx * vx + vy * vy + vz * vz);
+        g.px = geo[p].px; g.py = geo[p].py; g.pz = geo[p].pz;
+        g.ux = vx * inv; g.uy = vy * inv; g.uz = vz * inv;
+        g.dt = geo[p].dt; g.pad = 0.0;
+    }
+}
+
+hipError_t tdbp_pair_rc1(Tdbp* t, cf** rc1) {
+    TdbpPair* s = nullptr;
+    TCK(pair_scratch(t, &s));
+    *rc1 = s->rc1;
+    return hipSuccess;
+}
+
 hipError_t tdbp_pair(Tdbp* t, const float2* raw0, const float2* raw1, const double* pos, const double* vel, const double* t_pulses,
                      double t_start, const double* vel_focus, double scene_size, const sarx_tdbp_pair_params* prm, int chunks,
                      double2* d_img128, float2* d_img64, hipStream_t st) {
@@ -180,21 +192,13 @@ hipError_t tdbp_pair(Tdbp* t, const float2* raw0, const float2* raw1, const doub
     tdbp_pulse_table(t, pos, t_pulses, geo);               // position and dt = t_pulse - mean over all n_p
     int lo = 0, hi = t->n_s;
     bool series = true, tile = false;
-    pair_bounds(t, geo, u0, u1, vel_focus, t_start, scene_size, prm, &lo, &hi, &series, &tile);
+    tdbp_pair_bounds(t, geo, u0, u1, vel_focus, t_start, scene_size, prm, &lo, &hi, &series, &tile);
     tile = tile && tdbp_tile_ok(t, geo, vel_focus, scene_size);   // the d_tx series, and the switch SARX_TDBP_TILE=0
     if (t->full_rc) { lo = 0; hi = t->n_s; }
     TCK(tdbp_range_compress(t, raw0, t->rc, lo, hi, st));
     TCK(tdbp_range_compress(t, raw1, s->rc1, lo, hi, st)); // the same launches, the other destination
     TCK(tdbp_scratch_upload(s, st, [&](void* staging) {
-        PairGeo* h_geo = (PairGeo*)staging;
-        for (int p = 0; p < n_p; ++p) {
-            PairGeo& g = h_geo[p];
-            const double vx = vel[3 * p], vy = vel[3 * p + 1], vz = vel[3 * p + 2];
-            const double inv = 1.0 / sqrt(vx * vx + vy * vy + vz * vz);
-            g.px = geo[p].px; g.py = geo[p].py; g.pz = geo[p].pz;
-            g.ux = vx * inv; g.uy = vy * inv; g.uz = vz * inv;
-            g.dt = geo[p].dt; g.pad = 0.0;
-        }
+        tdbp_pair_table((PairGeo*)staging, geo, vel, n_p);
         return hipSuccess;
     }));
     TCK(tdbp_ensure_axes(t, scene_size, st));

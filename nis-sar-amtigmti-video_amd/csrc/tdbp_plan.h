@@ -5,6 +5,7 @@
 
 #include "tdbp_pixel.hpp"
 #include "tdbp_pair.h"
+#include "tdbp_pair_search.h"
 #include "tdbp_search.h"
 
 namespace sarx {
@@ -13,6 +14,12 @@ struct PulseGeo {            // one 64-byte record per pulse, read with scalar l
     double px, py, pz;       // platform position
     double wx, wy, wz;       // platform velocity - focus velocity  (v_rel, :211)
     double dt, pad;          // t_pulse - mean(t_pulses) (:203-204); pad = |v_rel|^2
+};
+
+struct PairGeo {             // the pair's table (tdbp_pair.hip, tdbp_pair_search.hip): one 64-byte record per pulse
+    double px, py, pz;       // transmitter
+    double ux, uy, uz;       // v^ = vel_tx / |vel_tx|
+    double dt, pad;
 };
 
 struct Tdbp {
@@ -38,6 +45,7 @@ struct Tdbp {
     uint64_t bytes = 0;
     TdbpSearch* search = nullptr; // scratch of the focus-velocity search (tdbp_search.hip), made by its first call, freed by tdbp_destroy
     TdbpPair* pair = nullptr;     // scratch of the two-receiver pair (tdbp_pair.hip), likewise
+    TdbpPairSearch* pair_search = nullptr;   // scratch of the search on the pair (tdbp_pair_search.hip), likewise
 };
 
 #define TCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
@@ -57,6 +65,14 @@ bool tdbp_tile_ok(const Tdbp* t, const std::vector<PulseGeo>& geo, const double*
 void moved_rect_range(const PulseGeo& g, const double* vf, double h, double* dmin, double* dmax);
 void tdbp_clamp_window(double imin, double imax, int n_s, int* lo, int* hi);
 double tdbp_tile_reach(const Tdbp* t, double scene_size);
+// the pair's own bounds over the pulses [u0, u1) for one focus velocity (tdbp_pair.hip): the sample window either channel can touch,
+// whether the series of tdbp_pair_pixel holds, and whether the pair's part of the tile expansion does
+void tdbp_pair_bounds(const Tdbp* t, const std::vector<PulseGeo>& geo, int u0, int u1, const double* vf, double t_start, double scene_size,
+                      const sarx_tdbp_pair_params* prm, int* lo, int* hi, bool* series, bool* tile);
+// the pair's table from the pulse table and the transmitter's velocity rows (none zero)
+void tdbp_pair_table(PairGeo* h_geo, const std::vector<PulseGeo>& geo, const double* vel, int n_p);
+// the pair scratch's buffer of channel 1's range-compressed pulses [n_p][n_s] (made with the scratch by the first call)
+hipError_t tdbp_pair_rc1(Tdbp* t, cf** rc1);
 // pulse chunks of one search or pair call, and the pulses in each; requested < 1: chosen here
 int tdbp_pick_chunks(int tiles, int blocks_per_chunk, int n_pulses, int requested, int* per_chunk);
 

@@ -369,6 +369,32 @@ TDBP_PAIR_SIGNATURES = {
     "sarx_tdbp_pair_route": (_i, [_vp, _P(_i)]),
 }
 
+# include/sarx_tdbp_pair_search.h: the focus-velocity search on the pair per GMTI report, a twelfth table bound the same way
+TDBP_PAIR_SEARCH_MAX_HYP, TDBP_PAIR_SEARCH_MIN_CHIP, TDBP_PAIR_SEARCH_MAX_CHIP = 64, 4, 64      # SARX_TDBP_PAIR_SEARCH_MAX_HYP, _MIN_CHIP, _MAX_CHIP
+TDBP_PAIR_SEARCH_MAX_CHIPS = 65535                                                              # SARX_TDBP_PAIR_SEARCH_MAX_CHIPS
+TDBP_PAIR_SEARCH_DPCA, TDBP_PAIR_SEARCH_CH0 = 0, 1
+
+
+class TdbpPairSearchParams(C.Structure):
+    """sarx_tdbp_pair_search_params (16 bytes)"""
+    _fields_ = [("chip_x", C.c_int32), ("chip_y", C.c_int32), ("n_hyp", C.c_int32), ("source", C.c_int32)]
+
+
+class TdbpPairSearchBest(C.Structure):
+    """sarx_tdbp_pair_search_best (80 bytes)"""
+    _fields_ = [("k_best", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("peak_ix", C.c_int32), ("peak_iy", C.c_int32),
+                ("reserved", C.c_int32), ("s4_prev", C.c_double), ("s4_best", C.c_double), ("s4_next", C.c_double),
+                ("interf_re", C.c_double), ("interf_im", C.c_double), ("p0", C.c_double), ("p1", C.c_double)]
+
+
+_PAIR_SEARCH_ARGS = [_vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _P(TdbpPairParams), _vp, _vp, _vp, _i, _P(TdbpPairSearchParams), _vp, _vp, _vp]
+TDBP_PAIR_SEARCH_SIGNATURES = {
+    "sarx_tdbp_pair_search_check": (_i, [_P(TdbpPairSearchParams), _i, _i]),
+    "sarx_tdbp_pair_search_dev": (_i, _PAIR_SEARCH_ARGS),
+    "sarx_tdbp_pair_search_host": (_i, _PAIR_SEARCH_ARGS),
+    "sarx_tdbp_pair_search_route": (_i, [_vp, _P(_i)]),
+}
+
 _lib = None
 
 
@@ -384,7 +410,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
             list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()) + \
             list(CLUSTER_SIGNATURES.items()) + list(ATIGATE_SIGNATURES.items()) + list(TDBP_SEARCH_SIGNATURES.items()) + \
-            list(TDBP_PAIR_SIGNATURES.items()):
+            list(TDBP_PAIR_SIGNATURES.items()) + list(TDBP_PAIR_SEARCH_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

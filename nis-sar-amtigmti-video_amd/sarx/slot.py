@@ -5,7 +5,7 @@ slot: a 16-byte sarx_gmti_header (count, overflow, two reserved words) followed 
 Overflow rule.  `count` is the number of cells that qualified, `overflow` is set when the list could not hold them, md is the
 slot's capacity.  What each reader does with them - every site keeps the condition it was written with:
   raise on overflow or count > md   gmti.decode_slot = decode, refocus.refocus_slot, TwoChannelBatch.plots,
-  (raise_if_overflowed, strict)     TwoChannelBatch.refocus
+  (raise_if_overflowed, strict)     TwoChannelBatch.refocus, tdbp_pair_search.tdbp_pair_search
   raise on overflow alone           atigate.gmti_ati_gate (the gated slot), cluster.GmtiPlots, cluster.fetch_plots (the plot slot)
   (raise_if_overflowed, not strict)
   clamp to min(count, md)           fetch = gmti.fetch_slot (the header itself is kept as it is), track._slot_ij
