@@ -1,4 +1,4 @@
-// What the host units of the C ABI share (api_ctx.hip, api_csa.hip, api_focus.hip, api_comm.hip, api_gmti.hip, api_balance.hip, api_track.hip, api_coherence.hip, api_oscfar.hip, api_cluster.hip, api_atigate.hip, api_tdbp_search.hip, api_tdbp_pair.hip): the context behind
+// What the host units of the C ABI share (api_ctx.hip, api_csa.hip, api_focus.hip, api_comm.hip, api_gmti.hip, api_balance.hip, api_track.hip, api_coherence.hip, api_oscfar.hip, api_cluster.hip, api_atigate.hip, api_tdbp_search.hip, api_tdbp_pair.hip, api_tdbp_pair_search.hip - these three through api_tdbp.h): the context behind
 // sarx_ctx*, error reporting, the exception guard and the staged host copies.  Host only: no kernel file includes this header.
 #pragma once
 #include "../../include/sarx.h"

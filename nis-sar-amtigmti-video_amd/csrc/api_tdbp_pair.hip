@@ -1,26 +1,9 @@
 // libsarx C ABI of include/sarx_tdbp_pair.h: argument checks and the launches of tdbp_pair.hip.
 #include "../../include/sarx_tdbp_pair.h"
-#include "api_ctx.h"
+#include "api_tdbp.h"
 #include "tdbp_pair.h"
 
-#include <cmath>
-
 using namespace sarx;
-
-// what can be said of the parameter block alone; n_pulses < 0: the pulse count is not known yet, the upper end is checked later
-static int params_check(sarx_ctx* c, int n_pulses, const sarx_tdbp_pair_params* k) {
-    if (!k) return fail(c, SARX_ERR_INVALID, "NULL pointer");
-    if (!std::isfinite(k->rx_offset_m[0]) || !std::isfinite(k->rx_offset_m[1])) return fail(c, SARX_ERR_INVALID, "rx_offset_m must be finite");
-    if (!std::isfinite(k->chirp_centre_s)) return fail(c, SARX_ERR_INVALID, "chirp_centre_s must be finite");
-    if (k->n_used < 1) return fail(c, SARX_ERR_INVALID, "n_used %d must be >= 1", k->n_used);
-    for (int ch = 0; ch < 2; ++ch) {
-        if (k->first_pulse[ch] < 0) return fail(c, SARX_ERR_INVALID, "first_pulse[%d] = %d must be >= 0", ch, k->first_pulse[ch]);
-        if (n_pulses >= 0 && (long long)k->first_pulse[ch] + k->n_used > n_pulses)
-            return fail(c, SARX_ERR_INVALID, "channel %d: pulses %d .. %lld lie outside [0, %d]", ch, k->first_pulse[ch],
-                        (long long)k->first_pulse[ch] + k->n_used, n_pulses);
-    }
-    return SARX_OK;
-}
 
 // Everything that can be refused without reading the plan is refused first, so a caller without a device gets the same answers.
 // The plan next: NULL, or not (or no longer) one that sarx_tdbp_plan_create returned.  Last what needs the plan's pulse count: the
@@ -33,24 +16,18 @@ static int pair_check(sarx_tdbp_plan* p, bool pointers_ok, const double* vel_tx,
     if (((uintptr_t)img128 & 15) || ((uintptr_t)img64 & 7)) return fail(*c, SARX_ERR_INVALID, "misaligned images128 (16) or images64 (8)");
     for (int i = 0; i < 3; ++i)
         if (!std::isfinite(vel_focus[i])) return fail(*c, SARX_ERR_INVALID, "vel_focus has a non-finite component");
-    if (!(scene_size > 0 && std::isfinite(scene_size))) return fail(*c, SARX_ERR_INVALID, "scene_size must be positive");
-    const int rc = params_check(*c, -1, k);
-    if (rc != SARX_OK) return rc;
-    if (const int rc1 = tdbp_plan_usable(p, c)) return rc1;
-    const int rc2 = params_check(*c, p->n_p, k);
-    if (rc2 != SARX_OK) return rc2;
-    for (int i = 0; i < p->n_p; ++i) {
-        const double v2 = vel_tx[3 * i] * vel_tx[3 * i] + vel_tx[3 * i + 1] * vel_tx[3 * i + 1] + vel_tx[3 * i + 2] * vel_tx[3 * i + 2];
-        if (!(v2 > 0 && std::isfinite(v2))) return fail(*c, SARX_ERR_INVALID, "vel_tx row %d is zero or not finite", i);
-    }
-    return SARX_OK;
+    if (const int rc = tdbp_scene_check(*c, scene_size)) return rc;
+    if (const int rc = tdbp_pair_params_check(*c, -1, k)) return rc;
+    if (const int rc = tdbp_plan_usable(p, c)) return rc;
+    if (const int rc = tdbp_pair_params_check(*c, p->n_p, k)) return rc;
+    return tdbp_vel_tx_check(*c, vel_tx, p->n_p);
 }
 
 extern "C" {
 
 int sarx_tdbp_pair_check(int n_pulses, const sarx_tdbp_pair_params* params) {
     if (n_pulses < 1) return fail(nullptr, SARX_ERR_INVALID, "n_pulses %d must be >= 1", n_pulses);
-    return params_check(nullptr, n_pulses, params);
+    return tdbp_pair_params_check(nullptr, n_pulses, params);
 }
 
 int sarx_tdbp_pair_dev(sarx_tdbp_plan* p, const void* d_raw0, const void* d_raw1, const double* pos_tx, const double* vel_tx,
@@ -93,13 +70,7 @@ int sarx_tdbp_pair_host(sarx_tdbp_plan* p, const void* raw0, const void* raw1, c
 }
 
 int sarx_tdbp_pair_route(const sarx_tdbp_plan* p, int* tile) {
-    if (!tile) return fail(nullptr, SARX_ERR_INVALID, "NULL pointer");
-    sarx_ctx* c = nullptr;
-    if (const int rc = tdbp_plan_usable(p, &c)) return rc;
-    const int r = tdbp_pair_route(p->t);
-    if (r < 0) return fail(c, SARX_ERR_INVALID, "the plan has not run a pair call yet");
-    *tile = r;
-    return SARX_OK;
+    return tdbp_route_query(p, tdbp_pair_route, "the plan has not run a pair call yet", tile);
 }
 
 }  // extern "C"

@@ -1,21 +1,12 @@
 // libsarx C ABI of include/sarx_tdbp_pair_search.h: argument checks and the launches of tdbp_pair_search.hip.
 #include "../../include/sarx_tdbp_pair_search.h"
-#include "api_ctx.h"
+#include "api_tdbp.h"
 #include "tdbp_pair_search.h"
 
-#include <climits>
-#include <cmath>
 #include <string>
 #include <vector>
 
 using namespace sarx;
-
-// the pair's own parameter check (sarx_tdbp_pair_check leaves its message for a caller without a context): handed on to c
-static int pair_params_check(sarx_ctx* c, int n_pulses, const sarx_tdbp_pair_params* k) {
-    const int rc = sarx_tdbp_pair_check(n_pulses, k);
-    if (rc != SARX_OK && c) { const std::string msg = g_init_error; return fail(c, rc, "%s", msg.c_str()); }
-    return rc;
-}
 
 // what can be said of the search's parameter block; nx, ny < 1: the grid is not known yet, the chip is held to it later
 static int params_check(sarx_ctx* c, const sarx_tdbp_pair_search_params* k, int nx, int ny) {
@@ -47,18 +38,13 @@ static int search_check(sarx_tdbp_plan* p, bool pointers_ok, const double* vel_t
     if ((long long)max_det * k->n_hyp > SARX_TDBP_PAIR_SEARCH_MAX_CHIPS)
         return fail(*c, SARX_ERR_INVALID, "max_detections %d x n_hyp %d = %lld chips, more than %d", max_det, k->n_hyp,
                     (long long)max_det * k->n_hyp, SARX_TDBP_PAIR_SEARCH_MAX_CHIPS);
-    for (int i = 0; i < 3 * k->n_hyp; ++i)
-        if (!std::isfinite(vel_hyps[i])) return fail(*c, SARX_ERR_INVALID, "focus velocity %d has a non-finite component", i / 3);
-    if (!(scene_size > 0 && std::isfinite(scene_size))) return fail(*c, SARX_ERR_INVALID, "scene_size must be positive");
-    if (const int rc = pair_params_check(*c, INT_MAX, pair)) return rc;          // the pulse count is not known yet
+    if (const int rc = tdbp_hyps_check(*c, vel_hyps, k->n_hyp)) return rc;
+    if (const int rc = tdbp_scene_check(*c, scene_size)) return rc;
+    if (const int rc = tdbp_pair_params_check(*c, -1, pair)) return rc;          // the pulse count is not known yet
     if (const int rc = tdbp_plan_usable(p, c)) return rc;
-    if (const int rc = pair_params_check(*c, p->n_p, pair)) return rc;
+    if (const int rc = tdbp_pair_params_check(*c, p->n_p, pair)) return rc;
     if (const int rc = params_check(*c, k, p->nx, p->ny)) return rc;
-    for (int i = 0; i < p->n_p; ++i) {
-        const double v2 = vel_tx[3 * i] * vel_tx[3 * i] + vel_tx[3 * i + 1] * vel_tx[3 * i + 1] + vel_tx[3 * i + 2] * vel_tx[3 * i + 2];
-        if (!(v2 > 0 && std::isfinite(v2))) return fail(*c, SARX_ERR_INVALID, "vel_tx row %d is zero or not finite", i);
-    }
-    return SARX_OK;
+    return tdbp_vel_tx_check(*c, vel_tx, p->n_p);
 }
 
 // the launches; a combination whose partial sums do not fit is the caller's mistake, not the device's
@@ -145,13 +131,7 @@ int sarx_tdbp_pair_search_host(sarx_tdbp_plan* p, const void* raw0, const void* 
 }
 
 int sarx_tdbp_pair_search_route(const sarx_tdbp_plan* p, int* tile) {
-    if (!tile) return fail(nullptr, SARX_ERR_INVALID, "NULL pointer");
-    sarx_ctx* c = nullptr;
-    if (const int rc = tdbp_plan_usable(p, &c)) return rc;
-    const int r = tdbp_pair_search_route(p->t);
-    if (r < 0) return fail(c, SARX_ERR_INVALID, "the plan has not run a pair search yet");
-    *tile = r;
-    return SARX_OK;
+    return tdbp_route_query(p, tdbp_pair_search_route, "the plan has not run a pair search yet", tile);
 }
 
 }  // extern "C"

@@ -1,9 +1,7 @@
 // libsarx C ABI of include/sarx_tdbp_search.h: argument checks and the launches of tdbp_search.hip.
 #include "../../include/sarx_tdbp_search.h"
-#include "api_ctx.h"
+#include "api_tdbp.h"
 #include "tdbp_search.h"
-
-#include <cmath>
 
 using namespace sarx;
 
@@ -17,10 +15,9 @@ static int search_check(sarx_tdbp_plan* p, bool pointers_ok, const double* vel_h
     if (n_hyp < 1 || n_hyp > SARX_TDBP_SEARCH_MAX_HYP)
         return fail(*c, SARX_ERR_INVALID, "n_hyp %d must be 1 .. %d", n_hyp, SARX_TDBP_SEARCH_MAX_HYP);
     if (vel_hyps)
-        for (int i = 0; i < 3 * n_hyp; ++i)
-            if (!std::isfinite(vel_hyps[i]))
-                return fail(*c, SARX_ERR_INVALID, "focus velocity %d has a non-finite component", i / 3);
-    if (scene_size && !(*scene_size > 0 && std::isfinite(*scene_size))) return fail(*c, SARX_ERR_INVALID, "scene_size must be positive");
+        if (const int rc = tdbp_hyps_check(*c, vel_hyps, n_hyp)) return rc;
+    if (scene_size)
+        if (const int rc = tdbp_scene_check(*c, *scene_size)) return rc;
     return tdbp_plan_usable(p, c);
 }
 
@@ -61,13 +58,7 @@ int sarx_tdbp_search_host(sarx_tdbp_plan* p, const void* raw, const double* pos,
 }
 
 int sarx_tdbp_search_route(const sarx_tdbp_plan* p, int* tile) {
-    if (!tile) return fail(nullptr, SARX_ERR_INVALID, "NULL pointer");
-    sarx_ctx* c = nullptr;
-    if (const int rc = tdbp_plan_usable(p, &c)) return rc;
-    const int r = tdbp_search_route(p->t);
-    if (r < 0) return fail(c, SARX_ERR_INVALID, "the plan has not run a search yet");
-    *tile = r;
-    return SARX_OK;
+    return tdbp_route_query(p, tdbp_search_route, "the plan has not run a search yet", tile);
 }
 
 int sarx_tdbp_search_set_chunks(sarx_tdbp_plan* p, int chunks) {

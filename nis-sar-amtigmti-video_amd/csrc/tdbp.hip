@@ -18,7 +18,7 @@
 //     6.6e8 pixel-pulses per 512 x 512 x 2500 frame in 1.66 ms.
 //   3 what the search and the two-receiver pair (tdbp_pair.hip) share with the focus on the host, stated here once (tdbp_plan.h):
 //     tdbp_range_compress into a destination the caller names, the geometry bounds (moved_rect_range, tdbp_clamp_window,
-//     tdbp_tile_reach), the pulse chunks of one call (tdbp_pick_chunks) and the scratch either holds beside the plan (TdbpScratch).
+//     tdbp_tile_reach), the pulse chunks of one call (tdbp_pick_chunks) and the scratch either holds beside the plan (TdbpScratch, TdbpHypScratch).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -327,6 +327,18 @@ void tdbp_scratch_free(TdbpScratch* s) {
     hipFree(s->geo); hipFree(s->part);
     if (s->h_geo) hipHostFree(s->h_geo);
     if (s->up_done) hipEventDestroy(s->up_done);
+}
+
+hipError_t tdbp_hyp_scratch_init(TdbpHypScratch* s, int n_p, size_t bytes, int max_hyp) {
+    TCK(tdbp_scratch_init(s, n_p, bytes));
+    TCK(hipMalloc(&s->hyps, (size_t)max_hyp * 3 * sizeof(double)));
+    return hipHostMalloc(&s->h_hyps, (size_t)max_hyp * 3 * sizeof(double), hipHostMallocDefault);
+}
+
+void tdbp_hyp_scratch_free(TdbpHypScratch* s) {
+    tdbp_scratch_free(s);
+    hipFree(s->hyps);
+    if (s->h_hyps) hipHostFree(s->h_hyps);
 }
 
 static void linspace(double a, double b, int n, std::vector<double>& out) {     // numpy.linspace (:173-174)

@@ -14,7 +14,8 @@
 // Two forms of the geometry, as in tdbp.hip: the exact one (tdbp_pair_kernel), and the one expanded about the reference pixel of each
 // 16 x 16 tile (tdbp_pair_tile_kernel: one lane per pulse fills a 256-pulse batch of records in LDS, every pixel walks them), taken
 // when tdbp_tile_ok and pair_tile_ok bound its truncation error below 1e-9 m for both channels.  Same pulse order per pixel, same
-// fp64 accumulation.  Pulse chunks: tdbp_pick_chunks (tdbp.hip); pulse table, staging and partial images: a TdbpScratch (tdbp_plan.h).
+// fp64 accumulation.  Both pulse loops are tdbp_pixel.hpp's (tdbp_pair_pulses, tdbp_pair_tile_pulses): the search on the pair
+// (tdbp_pair_search.hip) runs them too.  Pulse chunks: tdbp_pick_chunks (tdbp.hip); pulse table, staging and partial images: a TdbpScratch (tdbp_plan.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -40,29 +41,21 @@ struct PairArgs {
     int nx, ny, per_chunk, chunks;
 };
 
+// the partial images of both channels for this workgroup's chunk = blockIdx.y
+__device__ __forceinline__ void store_partial(const PairArgs& a, const TdbpPix& px, double re0, double im0, double re1, double im1) {
+    if (!px.live) return;
+    const size_t n_pix = (size_t)a.nx * a.ny, at = (size_t)blockIdx.y * n_pix + (size_t)px.iy * a.nx + px.ix;
+    a.part[at] = make_double2(re0, im0);
+    a.part[(size_t)a.chunks * n_pix + at] = make_double2(re1, im1);
+}
+
 template <bool SERIES> __global__ __launch_bounds__(256) void tdbp_pair_kernel(PairArgs a) {
     const TdbpPix px = tdbp_pix(a.nx, a.ny);
     const double gx0 = a.xax[px.live ? px.ix : 0], gy0 = a.yax[px.live ? px.iy : 0];
     const int p0 = a.u0 + blockIdx.y * a.per_chunk, p1 = min(a.u1, p0 + a.per_chunk);
-    const int e0 = a.first[0] + a.n_used, e1 = a.first[1] + a.n_used;
     double re0 = 0.0, im0 = 0.0, re1 = 0.0, im1 = 0.0;
-    for (int p = p0; p < p1; ++p) {
-        const PairGeo g = a.geo[p];
-        const double dx = fma(a.vfx, g.dt, gx0) - g.px;
-        const double dy = fma(a.vfy, g.dt, gy0) - g.py;
-        const double dz = a.vfz * g.dt - g.pz;
-        const double s_tx = fma(dx, dx, fma(dy, dy, dz * dz));
-        const double inv_d = rsqrt(s_tx);                                                   // one reciprocal square root
-        const double d_tx = s_tx * inv_d;                                                   // for both channels
-        const double dv = g.ux * dx + g.uy * dy + g.uz * dz;
-        if (p >= a.first[0] && p < e0) tdbp_pair_pixel<SERIES>(a, a.ch[0], s_tx, inv_d, d_tx, dv, a.off[0], p, re0, im0);
-        if (p >= a.first[1] && p < e1) tdbp_pair_pixel<SERIES>(a, a.ch[1], s_tx, inv_d, d_tx, dv, a.off[1], p, re1, im1);
-    }
-    if (px.live) {
-        const size_t n_pix = (size_t)a.nx * a.ny, at = (size_t)blockIdx.y * n_pix + (size_t)px.iy * a.nx + px.ix;
-        a.part[at] = make_double2(re0, im0);
-        a.part[(size_t)a.chunks * n_pix + at] = make_double2(re1, im1);
-    }
+    tdbp_pair_pulses<SERIES>(a, a.vfx, a.vfy, a.vfz, gx0, gy0, p0, p1, re0, im0, re1, im1);
+    store_partial(a, px, re0, im0, re1, im1);
 }
 
 // the tile form (tdbp_pixel.hpp): one lane per pulse fills the batch's records, then every pixel walks them
@@ -71,30 +64,9 @@ __global__ __launch_bounds__(256) void tdbp_pair_tile_kernel(PairArgs a) {
     const TdbpPix px = tdbp_pix(a.nx, a.ny);
     const TdbpTileOffsets o = tdbp_tile_offsets(a.xax, a.yax, px, a.nx, a.ny);
     const int p0 = a.u0 + blockIdx.y * a.per_chunk, p1 = min(a.u1, p0 + a.per_chunk);
-    const int e0 = a.first[0] + a.n_used, e1 = a.first[1] + a.n_used;
-    const double two_inv_ns = 2.0 * a.inv_ns;
     double re0 = 0.0, im0 = 0.0, re1 = 0.0, im1 = 0.0;
-    for (int pb = p0; pb < p1; pb += TP_BATCH) {
-        const int nb = min(TP_BATCH, p1 - pb);
-        __syncthreads();                                   // the previous batch has been consumed
-        if ((int)threadIdx.x < nb) {
-            const PairGeo g = a.geo[pb + threadIdx.x];
-            const double dx = fma(a.vfx, g.dt, o.xc) - g.px, dy = fma(a.vfy, g.dt, o.yc) - g.py, dz = a.vfz * g.dt - g.pz;
-            s_tp[threadIdx.x] = tdbp_pair_tile_prologue(dx, dy, dz, g.ux, g.uy, g.uz, a.off[0], a.off[1]);
-        }
-        __syncthreads();
-        for (int k = 0; k < nb; ++k) {
-            const int p = pb + k;
-            const double d_tx = tdbp_pair_tile_dtx(s_tp[k], o.qx, o.qy, o.q2);
-            if (p >= a.first[0] && p < e0) tdbp_pair_tile_pixel(a, a.ch[0], s_tp[k], 0, d_tx, o.qx, o.qy, two_inv_ns, p, re0, im0);
-            if (p >= a.first[1] && p < e1) tdbp_pair_tile_pixel(a, a.ch[1], s_tp[k], 1, d_tx, o.qx, o.qy, two_inv_ns, p, re1, im1);
-        }
-    }
-    if (px.live) {
-        const size_t n_pix = (size_t)a.nx * a.ny, at = (size_t)blockIdx.y * n_pix + (size_t)px.iy * a.nx + px.ix;
-        a.part[at] = make_double2(re0, im0);
-        a.part[(size_t)a.chunks * n_pix + at] = make_double2(re1, im1);
-    }
+    tdbp_pair_tile_pulses(a, s_tp, a.vfx, a.vfy, a.vfz, o, p0, p1, re0, im0, re1, im1);
+    store_partial(a, px, re0, im0, re1, im1);
 }
 
 // part: [2][chunks][n_pix]; out128: [2][n_pix] or NULL; out64: [2][n_pix] or NULL
@@ -186,8 +158,8 @@ hipError_t tdbp_pair(Tdbp* t, const float2* raw0, const float2* raw1, const doub
     TdbpPair* s = nullptr;
     TCK(pair_scratch(t, &s));
     const int n_p = t->n_p;
-    const int u0 = prm->first_pulse[0] < prm->first_pulse[1] ? prm->first_pulse[0] : prm->first_pulse[1];
-    const int u1 = (prm->first_pulse[0] > prm->first_pulse[1] ? prm->first_pulse[0] : prm->first_pulse[1]) + prm->n_used;
+    int u0 = 0, u1 = 0;
+    tdbp_pair_union(prm, &u0, &u1);
     std::vector<PulseGeo> geo;
     tdbp_pulse_table(t, pos, t_pulses, geo);               // position and dt = t_pulse - mean over all n_p
     int lo = 0, hi = t->n_s;
@@ -209,15 +181,9 @@ hipError_t tdbp_pair(Tdbp* t, const float2* raw0, const float2* raw1, const doub
     const size_t n_pix = (size_t)t->nx * t->ny;
     TCK(grow(&s->part, &s->part_cap, 2 * (size_t)chunks * n_pix));
     PairArgs a{};
-    a.ch[0].rc = t->rc; a.ch[1].rc = s->rc1;
-    for (int c = 0; c < 2; ++c) {
-        a.ch[c].fc = t->k.fc; a.ch[c].half_w = (float)t->n_s / 2.0f; a.ch[c].n_s = t->n_s;
-        a.off[c] = prm->rx_offset_m[c]; a.first[c] = prm->first_pulse[c];
-    }
-    a.geo = (const PairGeo*)s->geo; a.xax = t->xax; a.yax = t->yax; a.part = s->part;
+    tdbp_pair_fill_args(t, s, s->rc1, t_start, prm, a);
+    a.part = s->part;
     a.vfx = vel_focus[0]; a.vfy = vel_focus[1]; a.vfz = vel_focus[2];
-    a.inv_c = 1.0 / t->k.c; a.fs = t->k.fs; a.t_start = t_start; a.chirp_centre = prm->chirp_centre_s; a.inv_ns = 1.0 / (double)t->n_s;
-    a.n_used = prm->n_used; a.u0 = u0; a.u1 = u1;
     a.nx = t->nx; a.ny = t->ny; a.per_chunk = per_chunk; a.chunks = chunks;
     if (tile) hipLaunchKernelGGL(tdbp_pair_tile_kernel, dim3(tiles, chunks), dim3(256), 0, st, a);
     else if (series) hipLaunchKernelGGL(tdbp_pair_kernel<true>, dim3(tiles, chunks), dim3(256), 0, st, a);

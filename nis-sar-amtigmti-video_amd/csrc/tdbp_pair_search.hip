@@ -6,9 +6,9 @@
 //     bound (tdbp_pair_bounds) over the whole grid - the chips are not known on the host.  Channel 0 lands in the plan's rc buffer,
 //     channel 1 in the pair scratch's.
 //   2 back-projection: grid (tiles of the chip) x (report * n_hyp + hypothesis) x (pulse chunk), one thread per chip pixel carrying
-//     BOTH channels, as tdbp_pair.hip's kernels do and with their statements.  A workgroup reads the slot's header and its report: past
-//     the count, on an overflowed slot or with the report outside the grid it leaves at once (before any barrier; the test is
-//     workgroup-uniform).  Partial chips [max_det][n_hyp][chunks][2][chip_y * chip_x].
+//     BOTH channels through the pulse loops tdbp_pair.hip's kernels run (tdbp_pair_pulses, tdbp_pair_tile_pulses of tdbp_pixel.hpp).
+//     A workgroup reads the slot's header and its report: past the count, on an overflowed slot or with the report outside the grid
+//     it leaves at once (before any barrier; the test is workgroup-uniform).  Partial chips [max_det][n_hyp][chunks][2][chip_y * chip_x].
 //     The exact form (tdbp_pair_search_kernel) and the one expanded about the reference pixel of each 16 x 16 tile OF THE CHIP
 //     (tdbp_pair_search_tile_kernel): tdbp_pix and tdbp_tile_offsets of tdbp_pixel.hpp on the chip's extent and the axis tables shifted to
 //     the chip's corner, so a pixel is never farther from its reference pixel than the grid's tiles allow and tdbp_tile_ok and the
@@ -24,7 +24,6 @@
 
 #include <cmath>
 #include <cstdio>
-#include <cstring>
 #include <string>
 #include <vector>
 
@@ -85,20 +84,8 @@ template <bool SERIES> __global__ __launch_bounds__(256) void tdbp_pair_search_k
     const double gx0 = a.xax[x0 + (px.live ? px.ix : 0)], gy0 = a.yax[y0 + (px.live ? px.iy : 0)];
     const double vfx = a.hyps[3 * h], vfy = a.hyps[3 * h + 1], vfz = a.hyps[3 * h + 2];
     const int p0 = a.u0 + blockIdx.z * a.per_chunk, p1 = min(a.u1, p0 + a.per_chunk);
-    const int e0 = a.first[0] + a.n_used, e1 = a.first[1] + a.n_used;
     double re0 = 0.0, im0 = 0.0, re1 = 0.0, im1 = 0.0;
-    for (int p = p0; p < p1; ++p) {                       // the statements of tdbp_pair_kernel
-        const PairGeo g = a.geo[p];
-        const double dx = fma(vfx, g.dt, gx0) - g.px;
-        const double dy = fma(vfy, g.dt, gy0) - g.py;
-        const double dz = vfz * g.dt - g.pz;
-        const double s_tx = fma(dx, dx, fma(dy, dy, dz * dz));
-        const double inv_d = rsqrt(s_tx);
-        const double d_tx = s_tx * inv_d;
-        const double dv = g.ux * dx + g.uy * dy + g.uz * dz;
-        if (p >= a.first[0] && p < e0) tdbp_pair_pixel<SERIES>(a, a.ch[0], s_tx, inv_d, d_tx, dv, a.off[0], p, re0, im0);
-        if (p >= a.first[1] && p < e1) tdbp_pair_pixel<SERIES>(a, a.ch[1], s_tx, inv_d, d_tx, dv, a.off[1], p, re1, im1);
-    }
+    tdbp_pair_pulses<SERIES>(a, vfx, vfy, vfz, gx0, gy0, p0, p1, re0, im0, re1, im1);
     store_partial(a, px, re0, im0, re1, im1);
 }
 
@@ -112,32 +99,16 @@ __global__ __launch_bounds__(256) void tdbp_pair_search_tile_kernel(PairSearchAr
     const TdbpTileOffsets o = tdbp_tile_offsets(a.xax + x0, a.yax + y0, px, a.chip_x, a.chip_y);
     const double vfx = a.hyps[3 * h], vfy = a.hyps[3 * h + 1], vfz = a.hyps[3 * h + 2];
     const int p0 = a.u0 + blockIdx.z * a.per_chunk, p1 = min(a.u1, p0 + a.per_chunk);
-    const int e0 = a.first[0] + a.n_used, e1 = a.first[1] + a.n_used;
-    const double two_inv_ns = 2.0 * a.inv_ns;
     double re0 = 0.0, im0 = 0.0, re1 = 0.0, im1 = 0.0;
-    for (int pb = p0; pb < p1; pb += TP_BATCH) {
-        const int nb = min(TP_BATCH, p1 - pb);
-        __syncthreads();                                   // the previous batch has been consumed
-        if ((int)threadIdx.x < nb) {
-            const PairGeo g = a.geo[pb + threadIdx.x];
-            const double dx = fma(vfx, g.dt, o.xc) - g.px, dy = fma(vfy, g.dt, o.yc) - g.py, dz = vfz * g.dt - g.pz;
-            s_tp[threadIdx.x] = tdbp_pair_tile_prologue(dx, dy, dz, g.ux, g.uy, g.uz, a.off[0], a.off[1]);
-        }
-        __syncthreads();
-        for (int k = 0; k < nb; ++k) {
-            const int p = pb + k;
-            const double d_tx = tdbp_pair_tile_dtx(s_tp[k], o.qx, o.qy, o.q2);
-            if (p >= a.first[0] && p < e0) tdbp_pair_tile_pixel(a, a.ch[0], s_tp[k], 0, d_tx, o.qx, o.qy, two_inv_ns, p, re0, im0);
-            if (p >= a.first[1] && p < e1) tdbp_pair_tile_pixel(a, a.ch[1], s_tp[k], 1, d_tx, o.qx, o.qy, two_inv_ns, p, re1, im1);
-        }
-    }
+    tdbp_pair_tile_pulses(a, s_tp, vfx, vfy, vfz, o, p0, p1, re0, im0, re1, im1);
     store_partial(a, px, re0, im0, re1, im1);
 }
 
 static constexpr int PM = 256;
 static constexpr unsigned NO_CHIP_PIXEL = ~0u;
 
-// One workgroup per (report, hypothesis) = blockIdx.x.
+// One workgroup per (report, hypothesis) = blockIdx.x.  The fold is tdbp_search_metric_kernel's on 256 threads and a 32-bit index, and
+// stays written out in both: as one shared function it moved this kernel's code and time (profiles/r21_tdbp_loops_resource_usage.txt).
 __global__ __launch_bounds__(PM) void tdbp_pair_search_metric_kernel(PairSearchArgs a) {
     __shared__ double s_s2[PM], s_s4[PM], s_pk[PM];
     __shared__ unsigned s_at[PM];
@@ -244,8 +215,7 @@ __global__ __launch_bounds__(64) void tdbp_pair_search_best_kernel(PairSearchArg
     if (lane == 0) a.best[r] = b;
 }
 
-struct TdbpPairSearch : TdbpScratch {                      // the table holds PairGeo
-    double *hyps = nullptr, *h_hyps = nullptr;             // [MAX_HYP][3], staged and uploaded with the table
+struct TdbpPairSearch : TdbpHypScratch {                   // the table holds PairGeo
     // staging of the host entry point, in double2 elements as grow counts them
     double2 *raw1 = nullptr, *slot = nullptr, *rec = nullptr, *best = nullptr, *chips = nullptr;
     size_t raw1_cap = 0, slot_cap = 0, rec_cap = 0, best_cap = 0, chips_cap = 0;
@@ -253,19 +223,15 @@ struct TdbpPairSearch : TdbpScratch {                      // the table holds Pa
 
 void tdbp_pair_search_free(TdbpPairSearch* s) {
     if (!s) return;
-    tdbp_scratch_free(s);
-    hipFree(s->hyps); hipFree(s->raw1); hipFree(s->slot); hipFree(s->rec); hipFree(s->best); hipFree(s->chips);
-    if (s->h_hyps) hipHostFree(s->h_hyps);
+    tdbp_hyp_scratch_free(s);
+    hipFree(s->raw1); hipFree(s->slot); hipFree(s->rec); hipFree(s->best); hipFree(s->chips);
     delete s;
 }
 
 static hipError_t pair_search_scratch(Tdbp* t, TdbpPairSearch** out) {
     if (!t->pair_search) {
         TdbpPairSearch* s = new TdbpPairSearch();
-        const size_t hyp_bytes = (size_t)SARX_TDBP_PAIR_SEARCH_MAX_HYP * 3 * sizeof(double);
-        hipError_t e = tdbp_scratch_init(s, t->n_p, sizeof(PairGeo));
-        if (e == hipSuccess) e = hipMalloc(&s->hyps, hyp_bytes);
-        if (e == hipSuccess) e = hipHostMalloc(&s->h_hyps, hyp_bytes, hipHostMallocDefault);
+        const hipError_t e = tdbp_hyp_scratch_init(s, t->n_p, sizeof(PairGeo), SARX_TDBP_PAIR_SEARCH_MAX_HYP);
         if (e != hipSuccess) { tdbp_pair_search_free(s); return e; }
         t->pair_search = s;
     }
@@ -279,8 +245,8 @@ hipError_t tdbp_pair_search(Tdbp* t, const float2* raw0, const float2* raw1, con
                             const sarx_tdbp_pair_search_params* sp, int chunks, sarx_tdbp_search_record* d_records,
                             sarx_tdbp_pair_search_best* d_best, double2* d_chips, std::string* why, hipStream_t st) {
     const int n_p = t->n_p, n_hyp = sp->n_hyp;
-    const int u0 = prm->first_pulse[0] < prm->first_pulse[1] ? prm->first_pulse[0] : prm->first_pulse[1];
-    const int u1 = (prm->first_pulse[0] > prm->first_pulse[1] ? prm->first_pulse[0] : prm->first_pulse[1]) + prm->n_used;
+    int u0 = 0, u1 = 0;
+    tdbp_pair_union(prm, &u0, &u1);
     // pulse chunks over the union's pulses, one chunk launching tiles x max_det x n_hyp workgroups; the partial chips must fit the cap
     const int tiles = ((sp->chip_x + 15) / 16) * ((sp->chip_y + 15) / 16);
     const size_t n_chip = (size_t)sp->chip_x * sp->chip_y;
@@ -318,23 +284,13 @@ hipError_t tdbp_pair_search(Tdbp* t, const float2* raw0, const float2* raw1, con
     if (t->full_rc) { lo = 0; hi = t->n_s; }
     TCK(tdbp_range_compress(t, raw0, t->rc, lo, hi, st));
     TCK(tdbp_range_compress(t, raw1, rc1, lo, hi, st));
-    TCK(tdbp_scratch_upload(s, st, [&](void* staging) {
-        tdbp_pair_table((PairGeo*)staging, geo, vel, n_p);
-        memcpy(s->h_hyps, vel_hyps, (size_t)n_hyp * 3 * sizeof(double));
-        return hipMemcpyAsync(s->hyps, s->h_hyps, (size_t)n_hyp * 3 * sizeof(double), hipMemcpyHostToDevice, st);
-    }));
+    TCK(tdbp_hyp_upload(s, vel_hyps, n_hyp, st, [&](void* staging) { tdbp_pair_table((PairGeo*)staging, geo, vel, n_p); }));
     TCK(tdbp_ensure_axes(t, scene_size, st));
     TCK(grow(&s->part, &s->part_cap, per_chunk_bytes / sizeof(double2) * n_chunks));
     PairSearchArgs a{};
-    a.ch[0].rc = t->rc; a.ch[1].rc = rc1;
-    for (int c = 0; c < 2; ++c) {
-        a.ch[c].fc = t->k.fc; a.ch[c].half_w = (float)t->n_s / 2.0f; a.ch[c].n_s = t->n_s;
-        a.off[c] = prm->rx_offset_m[c]; a.first[c] = prm->first_pulse[c];
-    }
-    a.geo = (const PairGeo*)s->geo; a.hyps = s->hyps; a.xax = t->xax; a.yax = t->yax;
+    tdbp_pair_fill_args(t, s, rc1, t_start, prm, a);
+    a.hyps = s->hyps;
     a.rep = d_reports; a.hdr = d_header; a.part = s->part; a.rec = d_records; a.best = d_best; a.chips = d_chips;
-    a.inv_c = 1.0 / t->k.c; a.fs = t->k.fs; a.t_start = t_start; a.chirp_centre = prm->chirp_centre_s; a.inv_ns = 1.0 / (double)t->n_s;
-    a.n_used = prm->n_used; a.u0 = u0; a.u1 = u1;
     a.nx = t->nx; a.ny = t->ny; a.chip_x = sp->chip_x; a.chip_y = sp->chip_y; a.n_hyp = n_hyp; a.max_det = max_det; a.source = sp->source;
     a.per_chunk = per_chunk; a.chunks = n_chunks;
     const dim3 grid(tiles, max_det * n_hyp, n_chunks);
@@ -350,8 +306,6 @@ hipError_t tdbp_pair_search(Tdbp* t, const float2* raw0, const float2* raw1, con
 }
 
 int tdbp_pair_search_route(const Tdbp* t) { return t->pair_search ? t->pair_search->route : -1; }
-
-static hipError_t grow_bytes(double2** buf, size_t* cap, size_t bytes) { return grow(buf, cap, (bytes + sizeof(double2) - 1) / sizeof(double2)); }
 
 hipError_t tdbp_pair_search_staging(Tdbp* t, int max_det, const sarx_tdbp_pair_search_params* sp, bool chips, PairSearchStaging* out) {
     TdbpPairSearch* s = nullptr;

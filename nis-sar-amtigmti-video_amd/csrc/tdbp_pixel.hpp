@@ -1,8 +1,9 @@
 // One pixel and pulse of the time-domain back-projection (sar_batch_sim.py:205-232), stated once for the focus kernels of tdbp.hip,
-// the focus-velocity search kernels of tdbp_search.hip and the two-receiver kernels of tdbp_pair.hip, with what stands around it in
-// every one of them: the tile and pixel coordinates of a thread (tdbp_pix), a pixel's offset from its tile's reference pixel
-// (tdbp_tile_offsets) and the fixed-order sum of a pixel's chunks (tdbp_sum_chunks).  A kernel keeps only where the focus velocity
-// v_f and w = v_plat - v_f come from, the batch loop of the tile form and the place of its partial image.
+// the focus-velocity search kernels of tdbp_search.hip, the two-receiver kernels of tdbp_pair.hip and their search per GMTI report
+// (tdbp_pair_search.hip), with what stands around it in every one of them: the tile and pixel coordinates of a thread (tdbp_pix), a
+// pixel's offset from its tile's reference pixel (tdbp_tile_offsets) and the fixed-order sum of a pixel's chunks (tdbp_sum_chunks).
+// A single-channel kernel keeps only where the focus velocity v_f and w = v_plat - v_f come from, the batch loop of the tile form and the
+// place of its partial image; the pair's whole pulse loops are here (tdbp_pair_pulses, tdbp_pair_tile_pulses) for its four kernels.
 // Every statement groups its operands as the reference parity (1e-4) was measured with: -ffp-contract=on fuses inside a statement
 // only, so splitting or merging one changes bits.
 #pragma once
@@ -159,6 +160,12 @@ struct PairChan {
     int n_s;
 };
 
+struct PairGeo {             // the pair's table: one 64-byte record per pulse, read with scalar loads
+    double px, py, pz;       // transmitter
+    double ux, uy, uz;       // v^ = vel_tx / |vel_tx|
+    double dt, pad;
+};
+
 template <bool SERIES, class A> __device__ __forceinline__ void tdbp_pair_pixel(const A& c, const PairChan& ch, double s_tx, double inv_d,
                                                                               double d_tx, double dv, double off, int p, double& acc_re,
                                                                               double& acc_im) {
@@ -174,6 +181,26 @@ template <bool SERIES, class A> __device__ __forceinline__ void tdbp_pair_pixel(
     const double idx_f = (tau - c.t_start + c.chirp_centre) * c.fs;
     const float xn = (float)(2.0 * (idx_f * c.inv_ns) - 1.0);
     tdbp_sample(ch, xn, tau, p, acc_re, acc_im);
+}
+
+// The pulses [p0, p1) of one pixel at (gx0, gy0) under the focus velocity vf, both channels.  A: PairArgs, PairSearchArgs; read here
+// beside what tdbp_pair_pixel reads: geo, ch[2], off[2], first[2], n_used - the fields tdbp_pair_fill_args (tdbp_plan.h) sets.  A
+// channel accumulates only inside its own pulse range (a wave-uniform test).
+template <bool SERIES, class A> __device__ __forceinline__ void tdbp_pair_pulses(const A& a, double vfx, double vfy, double vfz, double gx0, double gy0,
+                                                                               int p0, int p1, double& re0, double& im0, double& re1, double& im1) {
+    const int e0 = a.first[0] + a.n_used, e1 = a.first[1] + a.n_used;
+    for (int p = p0; p < p1; ++p) {
+        const PairGeo g = a.geo[p];
+        const double dx = fma(vfx, g.dt, gx0) - g.px;
+        const double dy = fma(vfy, g.dt, gy0) - g.py;
+        const double dz = vfz * g.dt - g.pz;
+        const double s_tx = fma(dx, dx, fma(dy, dy, dz * dz));
+        const double inv_d = rsqrt(s_tx);                                                   // one reciprocal square root
+        const double d_tx = s_tx * inv_d;                                                   // for both channels
+        const double dv = g.ux * dx + g.uy * dy + g.uz * dz;
+        if (p >= a.first[0] && p < e0) tdbp_pair_pixel<SERIES>(a, a.ch[0], s_tx, inv_d, d_tx, dv, a.off[0], p, re0, im0);
+        if (p >= a.first[1] && p < e1) tdbp_pair_pixel<SERIES>(a, a.ch[1], s_tx, inv_d, d_tx, dv, a.off[1], p, re1, im1);
+    }
 }
 
 // The pair with the geometry expanded about the tile's reference pixel, as tdbp_tile_prologue / tdbp_tile_pixel do it: per
@@ -229,6 +256,30 @@ template <class A> __device__ __forceinline__ void tdbp_pair_tile_pixel(const A&
     const double idx_f = (tau - c.t_start + c.chirp_centre) * c.fs;
     const float xn = (float)fma(idx_f, two_inv_ns, -1.0);
     tdbp_sample(ch, xn, tau, p, acc_re, acc_im);
+}
+
+// The pulses [p0, p1) in the tile form: one lane per pulse fills the batch's records s_tp [TP_BATCH] in LDS, then every pixel walks
+// them.  Every thread of the workgroup comes here, dead lanes too: the loop holds two barriers per batch.
+template <class A> __device__ __forceinline__ void tdbp_pair_tile_pulses(const A& a, PairTilePulse* s_tp, double vfx, double vfy, double vfz, const TdbpTileOffsets& o,
+                                                                       int p0, int p1, double& re0, double& im0, double& re1, double& im1) {
+    const int e0 = a.first[0] + a.n_used, e1 = a.first[1] + a.n_used;
+    const double two_inv_ns = 2.0 * a.inv_ns;
+    for (int pb = p0; pb < p1; pb += TP_BATCH) {
+        const int nb = min(TP_BATCH, p1 - pb);
+        __syncthreads();                                   // the previous batch has been consumed
+        if ((int)threadIdx.x < nb) {
+            const PairGeo g = a.geo[pb + threadIdx.x];
+            const double dx = fma(vfx, g.dt, o.xc) - g.px, dy = fma(vfy, g.dt, o.yc) - g.py, dz = vfz * g.dt - g.pz;
+            s_tp[threadIdx.x] = tdbp_pair_tile_prologue(dx, dy, dz, g.ux, g.uy, g.uz, a.off[0], a.off[1]);
+        }
+        __syncthreads();
+        for (int k = 0; k < nb; ++k) {
+            const int p = pb + k;
+            const double d_tx = tdbp_pair_tile_dtx(s_tp[k], o.qx, o.qy, o.q2);
+            if (p >= a.first[0] && p < e0) tdbp_pair_tile_pixel(a, a.ch[0], s_tp[k], 0, d_tx, o.qx, o.qy, two_inv_ns, p, re0, im0);
+            if (p >= a.first[1] && p < e1) tdbp_pair_tile_pixel(a, a.ch[1], s_tp[k], 1, d_tx, o.qx, o.qy, two_inv_ns, p, re1, im1);
+        }
+    }
 }
 
 }  // namespace sarx

@@ -1,5 +1,8 @@
-// The back-projection plan itself: what tdbp.hip, the focus-velocity search (tdbp_search.hip) and the two-receiver pair (tdbp_pair.hip) share and no other unit sees.
+// The back-projection plan itself: what tdbp.hip, the focus-velocity search (tdbp_search.hip), the two-receiver pair (tdbp_pair.hip) and
+// the search on the pair per GMTI report (tdbp_pair_search.hip) share and no other unit sees: the plan, the geometry bounds, the scratch a
+// unit holds (TdbpScratch; TdbpHypScratch with a hypothesis table) and the kernel arguments they have in common (tdbp_fill_args, tdbp_pair_fill_args).
 #pragma once
+#include <cstring>
 #include <map>
 #include <vector>
 
@@ -14,12 +17,6 @@ struct PulseGeo {            // one 64-byte record per pulse, read with scalar l
     double px, py, pz;       // platform position
     double wx, wy, wz;       // platform velocity - focus velocity  (v_rel, :211)
     double dt, pad;          // t_pulse - mean(t_pulses) (:203-204); pad = |v_rel|^2
-};
-
-struct PairGeo {             // the pair's table (tdbp_pair.hip, tdbp_pair_search.hip): one 64-byte record per pulse
-    double px, py, pz;       // transmitter
-    double ux, uy, uz;       // v^ = vel_tx / |vel_tx|
-    double dt, pad;
 };
 
 struct Tdbp {
@@ -88,12 +85,25 @@ struct TdbpScratch {
 hipError_t tdbp_scratch_init(TdbpScratch* s, int n_p, size_t bytes);   // n_p records of bytes each
 void tdbp_scratch_free(TdbpScratch* s);
 hipError_t grow(double2** buf, size_t* cap, size_t need);              // *buf holds at least need elements; the old content is not kept
+inline hipError_t grow_bytes(double2** buf, size_t* cap, size_t bytes) { return grow(buf, cap, (bytes + sizeof(double2) - 1) / sizeof(double2)); }
 // fill writes the staging once the previous call's uploads have left it (at once as a rule) and enqueues what else it stages; the table follows
 template <class F> hipError_t tdbp_scratch_upload(TdbpScratch* s, hipStream_t st, F fill) {
     TCK(hipEventSynchronize(s->up_done));
     TCK(fill(s->h_geo));
     TCK(hipMemcpyAsync(s->geo, s->h_geo, s->bytes, hipMemcpyHostToDevice, st));
     return hipEventRecord(s->up_done, st);
+}
+// The scratch of a search (TdbpSearch, TdbpPairSearch): the pulse table and a table of focus velocities [max_hyp][3] with its staging
+struct TdbpHypScratch : TdbpScratch { double *hyps = nullptr, *h_hyps = nullptr; };
+hipError_t tdbp_hyp_scratch_init(TdbpHypScratch* s, int n_p, size_t bytes, int max_hyp);
+void tdbp_hyp_scratch_free(TdbpHypScratch* s);
+// table writes the pulse table into its staging; the n_hyp <= max_hyp hypotheses are staged and uploaded with it
+template <class F> hipError_t tdbp_hyp_upload(TdbpHypScratch* s, const double* vel_hyps, int n_hyp, hipStream_t st, F table) {
+    return tdbp_scratch_upload(s, st, [&](void* staging) {
+        table(staging);
+        memcpy(s->h_hyps, vel_hyps, (size_t)n_hyp * 3 * sizeof(double));
+        return hipMemcpyAsync(s->hyps, s->h_hyps, (size_t)n_hyp * 3 * sizeof(double), hipMemcpyHostToDevice, st);
+    });
 }
 // the kernel arguments that the focus launch (TdbpArgs) and the search launch (SearchArgs) share
 template <class A> void tdbp_fill_args(const Tdbp* t, double t_start, int per_chunk, A& a) {
@@ -102,5 +112,22 @@ template <class A> void tdbp_fill_args(const Tdbp* t, double t_start, int per_ch
     a.k_shift = -t->k.fc * 2.0 / t->k.c / t->k.k_rate;
     a.inv_ns = 1.0 / (double)t->n_s; a.half_w = (float)t->n_s / 2.0f;
     a.n_p = t->n_p; a.n_s = t->n_s; a.nx = t->nx; a.ny = t->ny; a.per_chunk = per_chunk;
+}
+// the union [u0, u1) of the two channels' pulse ranges: what the pair's kernels loop over
+inline void tdbp_pair_union(const sarx_tdbp_pair_params* prm, int* u0, int* u1) {
+    *u0 = prm->first_pulse[0] < prm->first_pulse[1] ? prm->first_pulse[0] : prm->first_pulse[1];
+    *u1 = (prm->first_pulse[0] > prm->first_pulse[1] ? prm->first_pulse[0] : prm->first_pulse[1]) + prm->n_used;
+}
+// the kernel arguments that the pair's launch (PairArgs) and its search's launches (PairSearchArgs) share; s: whose table holds PairGeo
+template <class A> void tdbp_pair_fill_args(const Tdbp* t, const TdbpScratch* s, const cf* rc1, double t_start, const sarx_tdbp_pair_params* prm, A& a) {
+    a.ch[0].rc = t->rc; a.ch[1].rc = rc1;
+    for (int c = 0; c < 2; ++c) {
+        a.ch[c].fc = t->k.fc; a.ch[c].half_w = (float)t->n_s / 2.0f; a.ch[c].n_s = t->n_s;
+        a.off[c] = prm->rx_offset_m[c]; a.first[c] = prm->first_pulse[c];
+    }
+    a.n_used = prm->n_used;
+    tdbp_pair_union(prm, &a.u0, &a.u1);
+    a.geo = (const PairGeo*)s->geo; a.xax = t->xax; a.yax = t->yax;
+    a.inv_c = 1.0 / t->k.c; a.fs = t->k.fs; a.t_start = t_start; a.chirp_centre = prm->chirp_centre_s; a.inv_ns = 1.0 / (double)t->n_s;
 }
 }  // namespace sarx

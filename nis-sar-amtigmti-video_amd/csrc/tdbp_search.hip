@@ -13,11 +13,10 @@
 //     when a stack is asked for, and folds P = re^2 + im^2 (products and sum rounded one by one, so P is what fp64 NumPy gives)
 //     into s2 = sum P, s4 = sum P^2, the peak and its place: thread t takes pixels t, t + 1024, ... in rising order, then a
 //     binary tree over the 1024 threads in LDS.  No atomics: the same bits on every run, with or without the stack.
-// Pulse chunks: tdbp_pick_chunks (tdbp.hip); pulse table, its staging and the partial images: a TdbpScratch (tdbp_plan.h).
+// Pulse chunks: tdbp_pick_chunks (tdbp.hip); pulse and hypothesis tables, their staging and the partial images: a TdbpHypScratch (tdbp_plan.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 #include "tdbp_plan.h"
@@ -142,8 +141,7 @@ __global__ __launch_bounds__(MT) void tdbp_search_metric_kernel(const double2* p
     }
 }
 
-struct TdbpSearch : TdbpScratch {                          // the table holds SearchGeo
-    double *hyps = nullptr, *h_hyps = nullptr;             // [MAX_HYP][3], staged and uploaded with the table
+struct TdbpSearch : TdbpHypScratch {                       // the table holds SearchGeo
     sarx_tdbp_search_record* rec = nullptr;                // staging of the host entry point
     double2* stack = nullptr;
     size_t stack_cap = 0;
@@ -151,18 +149,15 @@ struct TdbpSearch : TdbpScratch {                          // the table holds Se
 
 void tdbp_search_free(TdbpSearch* s) {
     if (!s) return;
-    tdbp_scratch_free(s);
-    hipFree(s->hyps); hipFree(s->rec); hipFree(s->stack);
-    if (s->h_hyps) hipHostFree(s->h_hyps);
+    tdbp_hyp_scratch_free(s);
+    hipFree(s->rec); hipFree(s->stack);
     delete s;
 }
 
 static hipError_t search_scratch(Tdbp* t, TdbpSearch** out) {
     if (!t->search) {
         TdbpSearch* s = new TdbpSearch();
-        hipError_t e = tdbp_scratch_init(s, t->n_p, sizeof(SearchGeo));
-        if (e == hipSuccess) e = hipMalloc(&s->hyps, (size_t)SARX_TDBP_SEARCH_MAX_HYP * 3 * sizeof(double));
-        if (e == hipSuccess) e = hipHostMalloc(&s->h_hyps, (size_t)SARX_TDBP_SEARCH_MAX_HYP * 3 * sizeof(double), hipHostMallocDefault);
+        const hipError_t e = tdbp_hyp_scratch_init(s, t->n_p, sizeof(SearchGeo), SARX_TDBP_SEARCH_MAX_HYP);
         if (e != hipSuccess) { tdbp_search_free(s); return e; }
         t->search = s;
     }
@@ -196,7 +191,7 @@ hipError_t tdbp_search(Tdbp* t, const float2* raw, const double* pos, const doub
         if (tile) tile = tdbp_tile_ok(t, geo, vf, scene_size);
     }
     TCK(tdbp_range_compress(t, raw, t->rc, lo, hi, st));
-    TCK(tdbp_scratch_upload(s, st, [&](void* staging) {
+    TCK(tdbp_hyp_upload(s, vel_hyps, n_hyp, st, [&](void* staging) {
         SearchGeo* h_geo = (SearchGeo*)staging;
         for (int p = 0; p < n_p; ++p) {
             SearchGeo& g = h_geo[p];
@@ -204,8 +199,6 @@ hipError_t tdbp_search(Tdbp* t, const float2* raw, const double* pos, const doub
             g.vx = vel[3 * p]; g.vy = vel[3 * p + 1]; g.vz = vel[3 * p + 2];
             g.dt = geo[p].dt; g.pad = 0.0;
         }
-        memcpy(s->h_hyps, vel_hyps, (size_t)n_hyp * 3 * sizeof(double));
-        return hipMemcpyAsync(s->hyps, s->h_hyps, (size_t)n_hyp * 3 * sizeof(double), hipMemcpyHostToDevice, st);
     }));
     TCK(tdbp_ensure_axes(t, scene_size, st));
     // a chunk launches tiles x n_hyp workgroups: fewer chunks with more hypotheses, the partial images stay near 16384 workgroups x 4 KiB

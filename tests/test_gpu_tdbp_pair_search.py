@@ -233,6 +233,26 @@ def test_constructed_ties():
     assert list(zip(res.peak_ix, res.peak_iy)) == [(37, 27), (0, 0)] and np.all(res.interf == 0)
 
 
+def test_a_nan_channel_leaves_nan_records_and_no_peak():
+    """The 160-pulse scene with every sample of channel 0 NaN, one report, a 16 x 16 chip, two hypotheses: channel 0's chips are NaN,
+    so is every DPCA power, and no pixel becomes the peak.  The records are what the restatement says of the device's own chips;
+    of NaN sums alone the first hypothesis is the best, and what hangs on the peak is NaN."""
+    sc = pref.stationary_scene()
+    hyps = np.array([[0.0, 0.0, 0.0], [3.0, -8.0, 0.0]])
+    raw = [np.full_like(sc["raw"][0], complex(np.nan, np.nan)), sc["raw"][1]]
+    _set_chunks(sc, 0)
+    res = _search(sc, 360.0, True, [(35, 45)], hyps, (16, 16), "dpca", raw=raw, chips=True)
+    assert len(res) == 1 and np.isnan(res.chips[0, :, 0]).all() and np.isfinite(res.chips[0, :, 1]).all()
+    for h in range(2):
+        s2, s4, pk, ix, iy = ref.record(res.chips[0, h], int(res.x0[0]), int(res.y0[0]), ref.DPCA)
+        g = res.records[0, h]
+        assert np.isnan([s2, s4, pk]).all() and (ix, iy) == (-1, -1)
+        assert np.isnan([g["s2"], g["s4"], g["peak"]]).all() and (g["peak_ix"], g["peak_iy"]) == (ix, iy), h
+    g = res.best[0]
+    assert g["k_best"] == 0 and g["s4_prev"] == -1.0 and (g["peak_ix"], g["peak_iy"]) == (-1, -1)
+    assert np.isnan([g[f] for f in ("s4_best", "interf_re", "interf_im", "p0", "p1")]).all()
+
+
 def test_device_resident_raw_slot_and_outputs_and_the_host_entry_point(mover_runs):
     """Device raw and a device slot through the wrapper, and sarx_tdbp_pair_search_host on host memory, give the bits of the host
     arrays through the wrapper; the host entry point leaves the records of a report outside the grid as they were."""

@@ -176,6 +176,34 @@ def test_peak_ties_go_to_the_smaller_linear_index():
     assert rec["peak"][3] == 2.0 and (int(rec["peak_ix"][3]), int(rec["peak_iy"][3])) == (1, 0) and np.isnan(rec["s2"][3])
 
 
+def test_an_all_nan_image_has_a_nan_record_and_no_peak():
+    """The metric launch alone over a 33 x 17 stack of two hypotheses: the first image all NaN - no power compares greater than the
+    fold's start, so s2, s4 and the peak are NaN and the peak's place is (-1, -1) - the second finite, its record NumPy's."""
+    import sarx
+    from sarx import tdbp
+    mod = importlib.import_module("sarx.tdbp_search")
+    _ffi = importlib.import_module("sarx._ffi")
+    ctx = sarx.default_context()
+    k = tb.scaled_constants()
+    nx, ny = 33, 17
+    plan = tdbp.cached_plan(ctx, k, 160, tb.spotlight_window(k)[0], nx, ny)
+    rng = np.random.default_rng(7)
+    stack = rng.standard_normal((2, ny, nx)) + 1j * rng.standard_normal((2, ny, nx))
+    stack[0] = complex(np.nan, np.nan)
+    d_stack, d_rec = ctx.to_device(stack), ctx.alloc(2 * 32)
+    try:
+        _ffi.check(ctx.lib.sarx_tdbp_search_metric_dev(plan.h, d_stack.ptr, 2, d_rec.ptr), ctx.h)
+        rec = d_rec.download(np.uint8, (64,)).view(mod.RECORD_DTYPE)
+    finally:
+        d_stack.release()
+        d_rec.release()
+    assert np.isnan(rec["s2"][0]) and np.isnan(rec["s4"][0]) and np.isnan(rec["peak"][0])
+    assert (int(rec["peak_ix"][0]), int(rec["peak_iy"][0])) == (-1, -1)
+    want = ref.records(stack[1:])
+    assert (rec["peak"][1], rec["peak_ix"][1], rec["peak_iy"][1]) == (want["peak"][0], want["peak_ix"][0], want["peak_iy"][0])
+    assert abs(rec["s2"][1] - want["s2"][0]) <= 1e-12 * want["s2"][0] and abs(rec["s4"][1] - want["s4"][0]) <= 1e-12 * want["s4"][0]
+
+
 def test_records_are_bit_identical_with_and_without_the_stack_and_from_run_to_run(tile_case, exact_case):
     for case, (sc, hyps, _, first) in (("tile", tile_case), ("exact", exact_case)):
         nx, ny = first.images.shape[2], first.images.shape[1]
