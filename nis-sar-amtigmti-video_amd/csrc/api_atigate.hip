@@ -1,6 +1,6 @@
 // libsarx C ABI of include/sarx_atigate.h: parameter checks and the two launches of atigate.hip.
 #include "../../include/sarx_atigate.h"
-#include "api_ctx.h"
+#include "api_gmti.h"
 #include "atigate.h"
 
 #include <cmath>
@@ -36,38 +36,29 @@ static int atigate_check(sarx_ctx* c, const sarx_atigate_params* p) {
 
 int sarx_atigate_check(const sarx_atigate_params* p) { return atigate_check(nullptr, p); }
 
+static size_t stats_bytes(const sarx_atigate_params* p) { return (size_t)p->max_detections * sizeof(sarx_atigate_stat); }
+
 int sarx_atigate_stats_bytes(const sarx_atigate_params* p, size_t* out) {
-    if (!out) return fail(nullptr, SARX_ERR_INVALID, "out_bytes is NULL");
-    const int rc = atigate_check(nullptr, p);
-    if (rc != SARX_OK) return rc;
-    *out = (size_t)p->max_detections * sizeof(sarx_atigate_stat);
-    return SARX_OK;
+    return size_query(out, [&] { return atigate_check(nullptr, p); }, [&] { return stats_bytes(p); });
 }
 
 int sarx_atigate_step_dev(sarx_ctx* c, const sarx_atigate_params* p, const void* d_slc1, const void* d_slc2, int n_az, int n_rg,
                           const void* d_slot_in, void* d_slot_out, void* d_stats) {
     NEED_CTX(c);
     return guarded(c, [&] {
-        const int rc = atigate_check(c, p);
-        if (rc != SARX_OK) return rc;
-        if (!d_slc1 || !d_slc2 || !d_slot_in || !d_slot_out) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
-        if (n_az < 1 || n_rg < 1 || n_az > SARX_ATIGATE_MAX_DIM || n_rg > SARX_ATIGATE_MAX_DIM)
-            return fail(c, SARX_ERR_INVALID, "bad image size %d x %d", n_az, n_rg);
-        if (((uintptr_t)d_slc1 & 7) || ((uintptr_t)d_slc2 & 7) || ((uintptr_t)d_slot_in & 7) || ((uintptr_t)d_slot_out & 7) ||
-            ((uintptr_t)d_stats & 7))
-            return fail(c, SARX_ERR_INVALID, "misaligned image, slot or statistics (8-byte alignment)");
+        if (const int rc = atigate_check(c, p)) return rc;
+        const DevBuf bufs[] = {need(d_slc1, 8), need(d_slc2, 8), need(d_slot_in, 8), need(d_slot_out, 8), opt(d_stats, 8)};
+        if (const int rc = buffers_present(c, bufs)) return rc;
+        if (const int rc = plane_size_check(c, "image", n_az, n_rg, SARX_ATIGATE_MAX_DIM)) return rc;
+        if (const int rc = buffers_aligned(c, bufs, "misaligned image, slot or statistics (8-byte alignment)")) return rc;
         const size_t slot = gmti_slot_bytes(p->max_detections);
         const size_t img = (size_t)n_az * (size_t)n_rg * sizeof(float2);
-        const size_t rec = (size_t)p->max_detections * sizeof(sarx_atigate_stat);
-        if (ranges_overlap(d_slot_out, slot, d_slot_in, slot) || ranges_overlap(d_slot_out, slot, d_slc1, img) ||
-            ranges_overlap(d_slot_out, slot, d_slc2, img))
-            return fail(c, SARX_ERR_INVALID, "the ATI gate's output slot overlaps an input");
-        if (ranges_overlap(d_stats, rec, d_slot_in, slot) || ranges_overlap(d_stats, rec, d_slc1, img) ||
-            ranges_overlap(d_stats, rec, d_slc2, img) || ranges_overlap(d_stats, rec, d_slot_out, slot))
-            return fail(c, SARX_ERR_INVALID, "the ATI gate's statistics overlap an input or the output slot");
-        const int L = c->cur_lane;
-        if (!c->atigate_keep[L])                                  // once per lane; freed with the context
-            HIPCHK(c, hipMalloc((void**)&c->atigate_keep[L], (size_t)SARX_ATIGATE_MAX_DETECTIONS * sizeof(int32_t)));
+        const Span in[] = {{d_slot_in, slot}, {d_slc1, img}, {d_slc2, img}}, out_slot[] = {{d_slot_out, slot}};
+        const Span rest[] = {in[0], in[1], in[2], out_slot[0]}, stats[] = {{d_stats, stats_bytes(p)}};
+        if (const int rc = check_spans(c, in, out_slot, "the ATI gate's output slot overlaps an input", nullptr)) return rc;
+        if (const int rc = check_spans(c, rest, stats, "the ATI gate's statistics overlap an input or the output slot", nullptr)) return rc;
+        LaneScratch& keep = c->lane_scratch(sarx_ctx::ATIGATE_KEEP);      // its full size at once: allocated once per lane
+        if (const int rc = keep.grow(c, (size_t)SARX_ATIGATE_MAX_DETECTIONS * sizeof(int32_t))) return rc;
         AtiGateArgs a{};
         a.p = *p;
         a.a = (const float2*)d_slc1;
@@ -77,7 +68,7 @@ int sarx_atigate_step_dev(sarx_ctx* c, const sarx_atigate_params* p, const void*
         a.in = (const char*)d_slot_in;
         a.out = (char*)d_slot_out;
         a.stats = (sarx_atigate_stat*)d_stats;
-        a.keep = c->atigate_keep[L];
+        a.keep = (int32_t*)keep.p;
         HIPCHK(c, launch_atigate(a, c->stream));
         return (int)SARX_OK;
     });

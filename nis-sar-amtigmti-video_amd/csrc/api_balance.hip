@@ -1,6 +1,6 @@
 // libsarx C ABI of include/sarx_balance.h: parameter checks and the launches of balance.hip.
 #include "../../include/sarx_balance.h"
-#include "api_ctx.h"
+#include "api_gmti.h"
 #include "balance.h"
 
 #include <cfloat>
@@ -14,9 +14,7 @@ static constexpr int BALANCE_MAX_DIM = 1 << 20;      // rows / columns of an ima
 
 static int balance_check(sarx_ctx* c, const sarx_balance_params* p, int n_az, int n_rg) {
     if (!p) return fail(c, SARX_ERR_INVALID, "balance params is NULL");
-    if (n_az < 1 || n_rg < 1) return fail(c, SARX_ERR_INVALID, "bad image size %d x %d", n_az, n_rg);
-    if (n_az > BALANCE_MAX_DIM || n_rg > BALANCE_MAX_DIM)
-        return fail(c, SARX_ERR_UNSUPPORTED, "balance image size %d x %d exceeds %d per side", n_az, n_rg, BALANCE_MAX_DIM);
+    if (const int rc = plane_size_check(c, "image", n_az, n_rg, BALANCE_MAX_DIM, "balance")) return rc;
     if (p->block_az < SARX_BALANCE_MIN_BLOCK || p->block_az > SARX_BALANCE_MAX_BLOCK || p->block_rg < SARX_BALANCE_MIN_BLOCK ||
         p->block_rg > SARX_BALANCE_MAX_BLOCK)
         return fail(c, SARX_ERR_INVALID, "balance block %d x %d: each side must be %d .. %d", p->block_az, p->block_rg,
@@ -37,32 +35,27 @@ static int balance_check(sarx_ctx* c, const sarx_balance_params* p, int n_az, in
 int sarx_balance_check(const sarx_balance_params* p, int n_az, int n_rg) { return balance_check(nullptr, p, n_az, n_rg); }
 
 int sarx_balance_table_bytes(const sarx_balance_params* p, int n_az, int n_rg, size_t* out) {
-    if (!out) return fail(nullptr, SARX_ERR_INVALID, "out_bytes is NULL");
-    const int rc = balance_check(nullptr, p, n_az, n_rg);
-    if (rc != SARX_OK) return rc;
-    const BalanceGeom g = balance_geom(n_az, n_rg, p->block_az, p->block_rg);
-    *out = sizeof(sarx_balance_header) + (size_t)g.nb_az * g.nb_rg * sizeof(sarx_balance_record);
-    return SARX_OK;
+    return size_query(out, [&] { return balance_check(nullptr, p, n_az, n_rg); }, [&] {
+        const BalanceGeom g = balance_geom(n_az, n_rg, p->block_az, p->block_rg);
+        return table_bytes<sarx_balance_header, sarx_balance_record>((size_t)g.nb_az * g.nb_rg);
+    });
 }
 
 int sarx_balance_workspace_bytes(const sarx_balance_params* p, int n_az, int n_rg, size_t* out) {
-    if (!out) return fail(nullptr, SARX_ERR_INVALID, "out_bytes is NULL");
-    const int rc = balance_check(nullptr, p, n_az, n_rg);
-    if (rc != SARX_OK) return rc;
-    const BalanceGeom g = balance_geom(n_az, n_rg, p->block_az, p->block_rg);
-    *out = (size_t)g.nb_az * g.nb_rg * g.strips * sizeof(BalPartial);
-    return SARX_OK;
+    return size_query(out, [&] { return balance_check(nullptr, p, n_az, n_rg); }, [&] {
+        const BalanceGeom g = balance_geom(n_az, n_rg, p->block_az, p->block_rg);
+        return (size_t)g.nb_az * g.nb_rg * g.strips * sizeof(BalPartial);
+    });
 }
 
 int sarx_balance_estimate_dev(sarx_ctx* c, const void* d_slc1, const void* d_slc2, int n_az, int n_rg, const sarx_balance_params* p,
                               void* d_table, void* d_workspace) {
     NEED_CTX(c);
     return guarded(c, [&] {
-        const int rc = balance_check(c, p, n_az, n_rg);
-        if (rc != SARX_OK) return rc;
-        if (!d_slc1 || !d_slc2 || !d_table || !d_workspace) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
-        if (((uintptr_t)d_slc1 & 7) || ((uintptr_t)d_slc2 & 7) || ((uintptr_t)d_table & 7) || ((uintptr_t)d_workspace & 7))
-            return fail(c, SARX_ERR_INVALID, "misaligned image, table or workspace (8-byte alignment)");
+        if (const int rc = balance_check(c, p, n_az, n_rg)) return rc;
+        if (const int rc = buffers_ok(c, {need(d_slc1, 8), need(d_slc2, 8), need(d_table, 8), need(d_workspace, 8)},
+                                      "misaligned image, table or workspace (8-byte alignment)"))
+            return rc;
         BalanceEstimateArgs a{};
         a.s1 = (const float2*)d_slc1; a.s2 = (const float2*)d_slc2;
         a.g = balance_geom(n_az, n_rg, p->block_az, p->block_rg);
@@ -70,7 +63,7 @@ int sarx_balance_estimate_dev(sarx_ctx* c, const void* d_slc1, const void* d_slc
         a.mode = p->mode; a.min_count = p->min_count; a.min_coherence = p->min_coherence;
         a.part = (BalPartial*)d_workspace;
         a.hdr = (sarx_balance_header*)d_table;
-        a.rec = (sarx_balance_record*)((char*)d_table + sizeof(sarx_balance_header));
+        a.rec = records_of<sarx_balance_header, sarx_balance_record>(d_table);
         HIPCHK(c, launch_balance_estimate(a, c->stream));
         return (int)SARX_OK;
     });
@@ -80,13 +73,11 @@ int sarx_balance_apply_dev(sarx_ctx* c, const void* d_slc1, const void* d_slc2, 
                            const void* d_table, void* d_slc2_out, float* d_dpca_mag) {
     NEED_CTX(c);
     return guarded(c, [&] {
-        const int rc = balance_check(c, p, n_az, n_rg);
-        if (rc != SARX_OK) return rc;
-        if (!d_slc2 || !d_table || !d_slc2_out) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
+        if (const int rc = balance_check(c, p, n_az, n_rg)) return rc;
+        const DevBuf bufs[] = {opt(d_slc1, 8), need(d_slc2, 8), need(d_table, 8), need(d_slc2_out, 8), opt(d_dpca_mag, 4)};
+        if (const int rc = buffers_present(c, bufs)) return rc;
         if (d_dpca_mag && !d_slc1) return fail(c, SARX_ERR_INVALID, "dpca_mag needs slc1");
-        if (((uintptr_t)d_slc1 & 7) || ((uintptr_t)d_slc2 & 7) || ((uintptr_t)d_table & 7) || ((uintptr_t)d_slc2_out & 7) ||
-            ((uintptr_t)d_dpca_mag & 3))
-            return fail(c, SARX_ERR_INVALID, "misaligned image, table (8-byte alignment) or dpca_mag (4-byte alignment)");
+        if (const int rc = buffers_aligned(c, bufs, "misaligned image, table (8-byte alignment) or dpca_mag (4-byte alignment)")) return rc;
         BalanceApplyArgs a{};
         a.s1 = d_dpca_mag ? (const float2*)d_slc1 : nullptr;
         a.s2 = (const float2*)d_slc2;
@@ -94,7 +85,7 @@ int sarx_balance_apply_dev(sarx_ctx* c, const void* d_slc1, const void* d_slc2, 
         a.dm = d_dpca_mag;
         a.g = balance_geom(n_az, n_rg, p->block_az, p->block_rg);
         a.interp = p->interp;
-        a.rec = (const sarx_balance_record*)((const char*)d_table + sizeof(sarx_balance_header));
+        a.rec = records_of<sarx_balance_header, const sarx_balance_record>(d_table);
         HIPCHK(c, launch_balance_apply(a, c->stream));
         return (int)SARX_OK;
     });

@@ -1,6 +1,6 @@
 // libsarx C ABI of include/sarx_cluster.h: parameter checks and the launch of cluster.hip.
 #include "../../include/sarx_cluster.h"
-#include "api_ctx.h"
+#include "api_gmti.h"
 #include "cluster.h"
 
 using namespace sarx;
@@ -19,30 +19,26 @@ static int cluster_check(sarx_ctx* c, const sarx_cluster_params* p) {
 
 int sarx_cluster_check(const sarx_cluster_params* p) { return cluster_check(nullptr, p); }
 
+static size_t plots_bytes(const sarx_cluster_params* p) { return (size_t)p->max_detections * sizeof(sarx_cluster_plot); }
+
 int sarx_cluster_plots_bytes(const sarx_cluster_params* p, size_t* out) {
-    if (!out) return fail(nullptr, SARX_ERR_INVALID, "out_bytes is NULL");
-    const int rc = cluster_check(nullptr, p);
-    if (rc != SARX_OK) return rc;
-    *out = (size_t)p->max_detections * sizeof(sarx_cluster_plot);
-    return SARX_OK;
+    return size_query(out, [&] { return cluster_check(nullptr, p); }, [&] { return plots_bytes(p); });
 }
 
 // n_frames >= 1; the strides are checked by the caller
 static int cluster_run(sarx_ctx* c, const sarx_cluster_params* p, const void* d_in, size_t in_stride, void* d_out, size_t out_stride,
                        int n_frames, void* d_plots, size_t plots_stride, int32_t* d_labels) {
-    if (!d_in || !d_out) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
-    if (((uintptr_t)d_in & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_plots & 7) || ((uintptr_t)d_labels & 3))
-        return fail(c, SARX_ERR_INVALID, "misaligned slot, plot records (8-byte alignment) or labels (4-byte alignment)");
+    const DevBuf bufs[] = {need(d_in, 8), need(d_out, 8), opt(d_plots, 8), opt(d_labels, 4)};
+    if (const int rc = buffers_ok(c, bufs, "misaligned slot, plot records (8-byte alignment) or labels (4-byte alignment)")) return rc;
     const size_t slot = gmti_slot_bytes(p->max_detections);
     const size_t last = (size_t)(n_frames - 1);
-    const size_t in_span = last * in_stride + slot, out_span = last * out_stride + slot;
-    const size_t plots_span = last * plots_stride + (size_t)p->max_detections * sizeof(sarx_cluster_plot);
-    const size_t labels_span = (size_t)n_frames * p->max_detections * sizeof(int32_t);
-    if (ranges_overlap(d_in, in_span, d_out, out_span)) return fail(c, SARX_ERR_INVALID, "cluster input and output slots overlap");
-    if (ranges_overlap(d_in, in_span, d_plots, plots_span) || ranges_overlap(d_in, in_span, d_labels, labels_span))
-        return fail(c, SARX_ERR_INVALID, "cluster plot records or labels overlap the input");
-    if (n_frames == 1 && (ranges_overlap(d_out, slot, d_plots, plots_span) || ranges_overlap(d_out, slot, d_labels, labels_span)))
-        return fail(c, SARX_ERR_INVALID, "cluster plot records or labels overlap the output slot");
+    // in, out and side: the strided extents over all frames; a lone frame's side outputs are held against its output slot as well
+    const Span in[] = {{d_in, last * in_stride + slot}}, out[] = {{d_out, last * out_stride + slot}};
+    const Span side[] = {{d_plots, last * plots_stride + plots_bytes(p)}, {d_labels, (size_t)n_frames * p->max_detections * sizeof(int32_t)}};
+    if (const int rc = check_spans(c, in, out, "cluster input and output slots overlap", nullptr)) return rc;
+    if (const int rc = check_spans(c, in, side, "cluster plot records or labels overlap the input", nullptr)) return rc;
+    if (n_frames == 1)
+        if (const int rc = check_spans(c, out, side, "cluster plot records or labels overlap the output slot", nullptr)) return rc;
     ClusterArgs a{};
     a.p = *p;
     a.in = (const char*)d_in;
@@ -60,8 +56,7 @@ int sarx_cluster_step_dev(sarx_ctx* c, const sarx_cluster_params* p, const void*
                           int32_t* d_labels) {
     NEED_CTX(c);
     return guarded(c, [&] {
-        const int rc = cluster_check(c, p);
-        if (rc != SARX_OK) return rc;
+        if (const int rc = cluster_check(c, p)) return rc;
         return cluster_run(c, p, d_slot_in, 0, d_slot_out, 0, 1, d_plots, 0, d_labels);
     });
 }
@@ -70,20 +65,15 @@ int sarx_cluster_run_dev(sarx_ctx* c, const sarx_cluster_params* p, const void* 
                          size_t out_stride_bytes, int n_frames, void* d_plots, size_t plots_stride_bytes, int32_t* d_labels) {
     NEED_CTX(c);
     return guarded(c, [&] {
-        const int rc = cluster_check(c, p);
-        if (rc != SARX_OK) return rc;
+        if (const int rc = cluster_check(c, p)) return rc;
         if (n_frames < 0) return fail(c, SARX_ERR_INVALID, "cluster n_frames must be >= 0");
-        const size_t slot = gmti_slot_bytes(p->max_detections);
-        if (in_stride_bytes < slot || (in_stride_bytes & 7) || out_stride_bytes < slot || (out_stride_bytes & 7))
+        const size_t slot = gmti_slot_bytes(p->max_detections), rec = plots_bytes(p);
+        if (!stride_ok(in_stride_bytes, slot) || !stride_ok(out_stride_bytes, slot))
             return fail(c, SARX_ERR_INVALID, "cluster slot strides %zu, %zu must be multiples of 8 and at least the slot's %zu bytes",
                         in_stride_bytes, out_stride_bytes, slot);
-        const size_t rec = (size_t)p->max_detections * sizeof(sarx_cluster_plot);
-        if (d_plots && (plots_stride_bytes < rec || (plots_stride_bytes & 7)))
+        if (d_plots && !stride_ok(plots_stride_bytes, rec))
             return fail(c, SARX_ERR_INVALID, "cluster plot stride %zu must be a multiple of 8 and at least %zu bytes", plots_stride_bytes, rec);
-        if (n_frames == 0) {
-            if (!d_in || !d_out) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
-            return (int)SARX_OK;
-        }
+        if (n_frames == 0) return buffers_present(c, {need(d_in, 8), need(d_out, 8)});
         return cluster_run(c, p, d_in, in_stride_bytes, d_out, out_stride_bytes, n_frames, d_plots, plots_stride_bytes, d_labels);
     });
 }

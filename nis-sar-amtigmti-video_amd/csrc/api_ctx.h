@@ -1,5 +1,7 @@
-// What the host units of the C ABI share (api_ctx.hip, api_csa.hip, api_focus.hip, api_comm.hip, api_gmti.hip, api_balance.hip, api_track.hip, api_coherence.hip, api_oscfar.hip, api_cluster.hip, api_atigate.hip, api_tdbp_search.hip, api_tdbp_pair.hip, api_tdbp_pair_search.hip - these three through api_tdbp.h): the context behind
-// sarx_ctx*, error reporting, the exception guard and the staged host copies.  Host only: no kernel file includes this header.
+// What the host units of the C ABI share (api_ctx.hip, api_csa.hip, api_focus.hip, api_comm.hip; the detection chain's api_gmti.hip,
+// api_oscfar.hip, api_cluster.hip, api_atigate.hip, api_track.hip, api_balance.hip, api_coherence.hip through api_gmti.h; the back-projection's
+// api_tdbp_search.hip, api_tdbp_pair.hip, api_tdbp_pair_search.hip through api_tdbp.h): the context behind sarx_ctx*, its per-lane scratch,
+// error reporting, the exception guard and the staged host copies.  Host only: no kernel file includes this header.
 #pragma once
 #include "../../include/sarx.h"
 #include "../../include/sarx_gmti.h"
@@ -16,6 +18,16 @@ typedef struct ncclComm* ncclComm_t;     // as <rccl/rccl.h> declares it; api_co
 constexpr double C_LIGHT = 299792458.0;     // sar_ati_dcpa_sim_csa.py:211
 constexpr int N_EVENTS = 256;
 constexpr int TW_MAX = 16384;
+
+struct sarx_ctx;
+namespace sarx {
+// Grow-only device scratch of one lane.  tdbp_plan.h's grow does the same for a plan; it lives with the kernels, which see no context.
+struct LaneScratch {
+    void* p = nullptr;
+    size_t cap = 0;                    // bytes p holds
+    int grow(sarx_ctx* c, size_t bytes);       // p holds at least bytes; what it held is not kept
+};
+}  // namespace sarx
 
 struct sarx_ctx {
     int device = -1;
@@ -65,11 +77,12 @@ struct sarx_ctx {
     int n_ranks = 0, rank = 0;
     int range_cus = 0;                 // > 0: persistent range launches size their grid for this many CUs (sarx_set_range_cus; frames in flight)
     int range_impl = 0;                // SARX_RANGE_IMPL: 0 auto, 1 = 16 pts/thread, 2 = 32 pts/thread split exchange, 3 = fused wave-private, 4 = sixteen-wave permuted-spectrum pair
-    sarx_gmti_report* gmti_copy[LANES] = {};   // sarx_gmti_refine_dev: the unordered list it sorts from, one per lane
-    size_t gmti_copy_cap[LANES] = {};          // reports it holds
-    float* refocus_curves[LANES] = {};         // sarx_refocus_dev without caller curves: the S_k the record launch reads, one per lane
-    size_t refocus_curves_cap[LANES] = {};     // floats it holds
-    int32_t* atigate_keep[LANES] = {};         // sarx_atigate_step_dev: the keep flags between its two launches, one set per lane
+    // device scratch that an entry point keeps between calls, one of each per lane (two frames in flight must not share it): the unordered
+    // report list sarx_gmti_refine_dev sorts from, the S_k that sarx_refocus_dev's record launch reads when the caller passes no curves, the
+    // keep flags between sarx_atigate_step_dev's two launches
+    enum Scratch { GMTI_COPY, REFOCUS_CURVES, ATIGATE_KEEP, N_SCRATCH };
+    sarx::LaneScratch scratch[N_SCRATCH][LANES];
+    sarx::LaneScratch& lane_scratch(Scratch k) { return scratch[k][cur_lane]; }
     std::string err;
 };
 
@@ -111,6 +124,16 @@ inline int tdbp_plan_raw(sarx_ctx* c, sarx_tdbp_plan* p) {
     if (!p->d_raw) HIPCHK(c, hipMalloc(&p->d_raw, n * sizeof(float2)));
     return SARX_OK;
 }
+// Frees only when p holds less than is asked, behind everything enqueued on the current lane; a frame loop allocates once per lane.
+inline int LaneScratch::grow(sarx_ctx* c, size_t bytes) {
+    if (bytes <= cap) return SARX_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipFree(p));
+    p = nullptr; cap = 0;
+    HIPCHK(c, hipMalloc(&p, bytes));
+    cap = bytes;
+    return SARX_OK;
+}
 
 // No C++ exception crosses the C ABI: entry points that allocate on the host (new, std::vector, std::string) run their body through
 // this guard; std::bad_alloc becomes SARX_ERR_NOMEM, anything else SARX_ERR_DEVICE, the message is set without allocating again.
@@ -134,13 +157,6 @@ hipError_t staged_copy(sarx_ctx* c, void* dst, const void* src, size_t bytes, bo
                        bool lane_only = false);
 bool is_page_locked(const void* p);
 
-// bytes of a GMTI slot: the header, then max_detections reports (include/sarx_gmti.h)
-inline size_t gmti_slot_bytes(int max_detections) { return sizeof(sarx_gmti_header) + (size_t)max_detections * sizeof(sarx_gmti_report); }
-// [a, a + na) and [b, b + nb) share a byte; a NULL pointer or an empty range overlaps nothing
-inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
 void comm_release(sarx_ctx* c);          // sarx_destroy's call into api_comm.hip: the communicator goes with the context
 
 }  // namespace sarx

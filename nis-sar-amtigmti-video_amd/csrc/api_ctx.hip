@@ -225,7 +225,8 @@ int sarx_destroy(sarx_ctx* c) {
     hipSetDevice(c->device);
     hipDeviceSynchronize();
     comm_release(c);
-    for (int k = 0; k < sarx_ctx::LANES; ++k) { hipFree(c->gmti_copy[k]); hipFree(c->refocus_curves[k]); hipFree(c->atigate_keep[k]); }
+    for (auto& kind : c->scratch)
+        for (LaneScratch& s : kind) hipFree(s.p);
     hipFree(c->tw_all); hipFree(c->ati_part_max_all); hipFree(c->ati_part_sum_all); hipFree(c->ati_out3_all); hipFree(c->power_part_all);
     for (int i = 0; i < N_EVENTS; ++i) hipEventDestroy(c->ev[i]);
     hipEventDestroy(c->comm_fence);

@@ -1,6 +1,6 @@
 // libsarx C ABI of include/sarx_oscfar.h: parameter checks and the launch of oscfar.hip.
 #include "../../include/sarx_oscfar.h"
-#include "api_ctx.h"
+#include "api_gmti.h"
 #include "oscfar.h"
 
 using namespace sarx;
@@ -13,9 +13,7 @@ static int oscfar_n_full(const sarx_gmti_params& b) {
 
 static int oscfar_check(sarx_ctx* c, const sarx_oscfar_params* p) {
     if (!p) return fail(c, SARX_ERR_INVALID, "OS-CFAR params is NULL");
-    size_t bytes = 0;
-    const int rc = sarx_gmti_slot_bytes(&p->base, &bytes);        // the CA launch's own refusals, word for word
-    if (rc != SARX_OK) return c ? fail(c, rc, "%s", sarx_last_error(nullptr)) : rc;
+    if (const int rc = gmti_check_params(c, &p->base)) return rc;        // the CA launch's own refusals, word for word
     if (p->flags != 0) return fail(c, SARX_ERR_INVALID, "OS-CFAR flags %d: none is defined", p->flags);
     const int nf = oscfar_n_full(p->base);
     if (p->rank < 1 || p->rank > nf) return fail(c, SARX_ERR_INVALID, "OS-CFAR rank %d must be 1 .. N_full = %d", p->rank, nf);
@@ -28,19 +26,14 @@ int sarx_gmti_oscfar_dev(sarx_ctx* c, const float* d_mag, int n_az, int n_rg, co
                          sarx_gmti_header* d_header) {
     NEED_CTX(c);
     return guarded(c, [&] {
-        const int rc = oscfar_check(c, p);
-        if (rc != SARX_OK) return rc;
-        if (!d_mag || !d_reports || !d_header) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
-        if (n_az < 1 || n_rg < 1) return fail(c, SARX_ERR_INVALID, "bad plane size %d x %d", n_az, n_rg);
-        if (((uintptr_t)d_mag & 3) || ((uintptr_t)d_reports & 7) || ((uintptr_t)d_header & 3))
-            return fail(c, SARX_ERR_INVALID, "misaligned plane, report list or header");
+        if (const int rc = oscfar_check(c, p)) return rc;
+        const DevBuf bufs[] = {need(d_mag, 4), need(d_reports, 8), need(d_header, 4)};
+        if (const int rc = buffers_present(c, bufs)) return rc;
+        if (const int rc = plane_size_check(c, "plane", n_az, n_rg)) return rc;
+        if (const int rc = buffers_aligned(c, bufs, "misaligned plane, report list or header")) return rc;
         OsCfarArgs a{};
-        const sarx_gmti_params& b = p->base;
-        a.base.m = d_mag; a.base.n_az = n_az; a.base.n_rg = n_rg;
-        a.base.ga = b.guard_az; a.base.gr = b.guard_rg; a.base.oa = b.guard_az + b.train_az; a.base.orr = b.guard_rg + b.train_rg;
-        a.base.alpha = b.alpha; a.base.min_train = b.min_train; a.base.max_det = b.max_detections;
-        a.base.rep = d_reports; a.base.hdr = d_header;
-        a.rank = p->rank; a.n_full = oscfar_n_full(b);
+        a.base = gmti_cfar_args(d_mag, n_az, n_rg, p->base, d_reports, d_header);
+        a.rank = p->rank; a.n_full = oscfar_n_full(p->base);
         HIPCHK(c, launch_gmti_oscfar(a, c->stream));
         return (int)SARX_OK;
     });

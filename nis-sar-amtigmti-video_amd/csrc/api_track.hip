@@ -1,6 +1,6 @@
 // libsarx C ABI of include/sarx_track.h: parameter checks and the launches of track.hip.
 #include "../../include/sarx_track.h"
-#include "api_ctx.h"
+#include "api_gmti.h"
 #include "track.h"
 
 #include <cmath>
@@ -30,30 +30,19 @@ static int track_check(sarx_ctx* c, const sarx_track_params* p) {
 int sarx_track_check(const sarx_track_params* p) { return track_check(nullptr, p); }
 
 int sarx_track_table_bytes(const sarx_track_params* p, size_t* out) {
-    if (!out) return fail(nullptr, SARX_ERR_INVALID, "out_bytes is NULL");
-    const int rc = track_check(nullptr, p);
-    if (rc != SARX_OK) return rc;
-    *out = sizeof(sarx_track_header) + (size_t)p->max_tracks * sizeof(sarx_track_slot);
-    return SARX_OK;
+    return size_query(out, [&] { return track_check(nullptr, p); }, [&] { return table_bytes<sarx_track_header, sarx_track_slot>(p->max_tracks); });
 }
 
 int sarx_track_workspace_bytes(const sarx_track_params* p, size_t* out) {
-    if (!out) return fail(nullptr, SARX_ERR_INVALID, "out_bytes is NULL");
-    const int rc = track_check(nullptr, p);
-    if (rc != SARX_OK) return rc;
-    *out = track_workspace_bytes(p->max_tracks, p->max_detections);
-    return SARX_OK;
+    return size_query(out, [&] { return track_check(nullptr, p); }, [&] { return track_workspace_bytes(p->max_tracks, p->max_detections); });
 }
 
 int sarx_track_init_dev(sarx_ctx* c, const sarx_track_params* p, void* d_table) {
     NEED_CTX(c);
     return guarded(c, [&] {
-        const int rc = track_check(c, p);
-        if (rc != SARX_OK) return rc;
-        if (!d_table) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
-        if ((uintptr_t)d_table & 7) return fail(c, SARX_ERR_INVALID, "misaligned track table (8-byte alignment)");
-        HIPCHK(c, launch_track_init((sarx_track_header*)d_table, (sarx_track_slot*)((char*)d_table + sizeof(sarx_track_header)),
-                                    p->max_tracks, c->stream));
+        if (const int rc = track_check(c, p)) return rc;
+        if (const int rc = buffers_ok(c, {need(d_table, 8)}, "misaligned track table (8-byte alignment)")) return rc;
+        HIPCHK(c, launch_track_init((sarx_track_header*)d_table, records_of<sarx_track_header, sarx_track_slot>(d_table), p->max_tracks, c->stream));
         return (int)SARX_OK;
     });
 }
@@ -63,9 +52,9 @@ static int track_step(sarx_ctx* c, const sarx_track_params* p, const void* d_slo
     TrackArgs a{};
     a.p = *p;
     a.slot_hdr = (const sarx_gmti_header*)d_slot;
-    a.rep = (const sarx_gmti_report*)((const char*)d_slot + sizeof(sarx_gmti_header));
+    a.rep = slot_reports(d_slot);
     a.hdr = (sarx_track_header*)d_table;
-    a.slots = (sarx_track_slot*)((char*)d_table + sizeof(sarx_track_header));
+    a.slots = records_of<sarx_track_header, sarx_track_slot>(d_table);
     a.assoc = d_assoc_row;
     a.best_r = (int32_t*)d_workspace;
     a.best_t = a.best_r + track_ws_words(p->max_tracks);
@@ -76,21 +65,17 @@ static int track_step(sarx_ctx* c, const sarx_track_params* p, const void* d_slo
 }
 
 static int track_buffers(sarx_ctx* c, const void* d_slots, const void* d_table, const void* d_assoc, const void* d_workspace) {
-    if (!d_slots || !d_table || !d_workspace) return fail(c, SARX_ERR_INVALID, "NULL device pointer");
-    if (((uintptr_t)d_slots & 7) || ((uintptr_t)d_table & 7) || ((uintptr_t)d_workspace & 7) || ((uintptr_t)d_assoc & 3))
-        return fail(c, SARX_ERR_INVALID, "misaligned slot, table, workspace (8-byte alignment) or assoc (4-byte alignment)");
-    return SARX_OK;
+    return buffers_ok(c, {need(d_slots, 8), need(d_table, 8), need(d_workspace, 8), opt(d_assoc, 4)},
+                      "misaligned slot, table, workspace (8-byte alignment) or assoc (4-byte alignment)");
 }
 
 int sarx_track_step_dev(sarx_ctx* c, const sarx_track_params* p, const void* d_slot, int frame_index, void* d_table, int32_t* d_assoc_row,
                         void* d_workspace) {
     NEED_CTX(c);
     return guarded(c, [&] {
-        int rc = track_check(c, p);
-        if (rc != SARX_OK) return rc;
+        if (const int rc = track_check(c, p)) return rc;
         if (frame_index < 0) return fail(c, SARX_ERR_INVALID, "track frame_index must be >= 0");
-        rc = track_buffers(c, d_slot, d_table, d_assoc_row, d_workspace);
-        if (rc != SARX_OK) return rc;
+        if (const int rc = track_buffers(c, d_slot, d_table, d_assoc_row, d_workspace)) return rc;
         return track_step(c, p, d_slot, frame_index, d_table, d_assoc_row, d_workspace);
     });
 }
@@ -99,19 +84,16 @@ int sarx_track_run_dev(sarx_ctx* c, const sarx_track_params* p, const void* d_st
                        int32_t* d_assoc, void* d_workspace) {
     NEED_CTX(c);
     return guarded(c, [&] {
-        int rc = track_check(c, p);
-        if (rc != SARX_OK) return rc;
+        if (const int rc = track_check(c, p)) return rc;
         if (n_frames < 0) return fail(c, SARX_ERR_INVALID, "track n_frames must be >= 0");
         const size_t slot = gmti_slot_bytes(p->max_detections);
-        if (slot_stride_bytes < slot || (slot_stride_bytes & 7))
+        if (!stride_ok(slot_stride_bytes, slot))
             return fail(c, SARX_ERR_INVALID, "track slot stride %zu must be a multiple of 8 and at least the slot's %zu bytes", slot_stride_bytes, slot);
-        rc = track_buffers(c, d_stack, d_table, d_assoc, d_workspace);
-        if (rc != SARX_OK) return rc;
-        for (int f = 0; f < n_frames; ++f) {
-            rc = track_step(c, p, (const char*)d_stack + (size_t)f * slot_stride_bytes, f, d_table,
-                            d_assoc ? d_assoc + (size_t)f * p->max_detections : nullptr, d_workspace);
-            if (rc != SARX_OK) return rc;
-        }
+        if (const int rc = track_buffers(c, d_stack, d_table, d_assoc, d_workspace)) return rc;
+        for (int f = 0; f < n_frames; ++f)
+            if (const int rc = track_step(c, p, (const char*)d_stack + (size_t)f * slot_stride_bytes, f, d_table,
+                                          d_assoc ? d_assoc + (size_t)f * p->max_detections : nullptr, d_workspace))
+                return rc;
         return (int)SARX_OK;
     });
 }
