@@ -26,7 +26,7 @@
  *    scratch           : belongs to the plan; made by the first call, a repeated call allocates nothing on the device.  As with
  *                        sarx_tdbp_focus_dev, a plan serves one lane at a time.
  *
- * Left out: more than two receivers, a velocity search on the pair, relocating movers on the ground grid, fusing the ATI / DPCA
+ * More than two receivers: sarx_tdbp_multi.h.  Left out: a velocity search on the pair, relocating movers on the ground grid, fusing the ATI / DPCA
  * planes into the reduce launch. */
 #ifndef SARX_TDBP_PAIR_H
 #define SARX_TDBP_PAIR_H

@@ -1,4 +1,5 @@
-// The refusals that api_tdbp_search.hip, api_tdbp_pair.hip and api_tdbp_pair_search.hip have in common, each message stated once.
+// The refusals that api_tdbp_search.hip, api_tdbp_pair.hip, api_tdbp_pair_search.hip and api_tdbp_multi.hip have in common, each message
+// stated once.
 // c: where the message goes (NULL: the caller has no live plan, sarx_last_error(NULL) gets it).
 #pragma once
 #include "../../include/sarx_tdbp_pair.h"

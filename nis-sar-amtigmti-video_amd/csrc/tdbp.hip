@@ -109,6 +109,7 @@ void tdbp_destroy(Tdbp* t) {
     tdbp_search_free(t->search);
     tdbp_pair_free(t->pair);
     tdbp_pair_search_free(t->pair_search);
+    tdbp_multi_free(t->multi);
     delete t;
 }
 

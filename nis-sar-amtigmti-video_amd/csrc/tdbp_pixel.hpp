@@ -3,7 +3,8 @@
 // (tdbp_pair_search.hip), with what stands around it in every one of them: the tile and pixel coordinates of a thread (tdbp_pix), a
 // pixel's offset from its tile's reference pixel (tdbp_tile_offsets) and the fixed-order sum of a pixel's chunks (tdbp_sum_chunks).
 // A single-channel kernel keeps only where the focus velocity v_f and w = v_plat - v_f come from, the batch loop of the tile form and the
-// place of its partial image; the pair's whole pulse loops are here (tdbp_pair_pulses, tdbp_pair_tile_pulses) for its four kernels.
+// place of its partial image; the pair's whole pulse loops are here (tdbp_pair_pulses, tdbp_pair_tile_pulses) for its four kernels, and
+// beside them the same loops for N = 2, 3 or 4 receivers (tdbp_multi_pulses, tdbp_multi_tile_pulses) for the kernels of tdbp_multi.hip.
 // Every statement groups its operands as the reference parity (1e-4) was measured with: -ffp-contract=on fuses inside a statement
 // only, so splitting or merging one changes bits.
 #pragma once
@@ -241,14 +242,14 @@ __device__ __forceinline__ PairTilePulse tdbp_pair_tile_prologue(double dx, doub
     return t;
 }
 
-// d_tx of one pixel and pulse, for both channels
-__device__ __forceinline__ double tdbp_pair_tile_dtx(const PairTilePulse& t, double qx, double qy, double q2) {
+// d_tx of one pixel and pulse, for every channel.  T: PairTilePulse, or MultiTilePulse<N> below (the same fields, N channels)
+template <class T> __device__ __forceinline__ double tdbp_pair_tile_dtx(const T& t, double qx, double qy, double q2) {
     const double u = fma(t.a1, qx, fma(t.a2, qy, q2)) * t.inv_d0sq;
     const double h = u * fma(u, fma(u, 1.0 / 16.0, -1.0 / 8.0), 0.5);
     return fma(t.d0, h, t.d0);
 }
 
-template <class A> __device__ __forceinline__ void tdbp_pair_tile_pixel(const A& c, const PairChan& ch, const PairTilePulse& t, int chan,
+template <class A, class T> __device__ __forceinline__ void tdbp_pair_tile_pixel(const A& c, const PairChan& ch, const T& t, int chan,
                                                                       double d_tx, double qx, double qy, double two_inv_ns, int p,
                                                                       double& acc_re, double& acc_im) {
     const double e = fma(t.ex[chan], qx, fma(t.ey[chan], qy, t.e0[chan]));                  // d_tx - d_rx
@@ -278,6 +279,87 @@ template <class A> __device__ __forceinline__ void tdbp_pair_tile_pulses(const A
             const double d_tx = tdbp_pair_tile_dtx(s_tp[k], o.qx, o.qy, o.q2);
             if (p >= a.first[0] && p < e0) tdbp_pair_tile_pixel(a, a.ch[0], s_tp[k], 0, d_tx, o.qx, o.qy, two_inv_ns, p, re0, im0);
             if (p >= a.first[1] && p < e1) tdbp_pair_tile_pixel(a, a.ch[1], s_tp[k], 1, d_tx, o.qx, o.qy, two_inv_ns, p, re1, im1);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// N = 2, 3 or 4 receivers (tdbp_multi.hip): the pair's geometry per channel, the transmit leg still computed once
+// per pixel and pulse.  Every channel's statements are the pair's own - the exact form calls tdbp_pair_pixel itself, the tile form
+// tdbp_pair_tile_dtx and tdbp_pair_tile_pixel on a record with N channels, and only the record's prologue is restated (operand for
+// operand, over N offsets) - so N = 2 gives the pair's bits.  A: MultiArgs; read here beside what tdbp_pair_pixel reads: geo, rc[N],
+// fc, half_w, n_s (one waveform for every channel: a PairChan is made of them per channel, so the arguments hold them once), off[N],
+// first[N], n_used.
+// ------------------------------------------------------------------------------------------------------------
+template <int N, bool SERIES, class A> __device__ __forceinline__ void tdbp_multi_pulses(const A& a, double vfx, double vfy, double vfz, double gx0,
+                                                                                        double gy0, int p0, int p1, double (&re)[N], double (&im)[N]) {
+    for (int p = p0; p < p1; ++p) {
+        const PairGeo g = a.geo[p];
+        const double dx = fma(vfx, g.dt, gx0) - g.px;
+        const double dy = fma(vfy, g.dt, gy0) - g.py;
+        const double dz = vfz * g.dt - g.pz;
+        const double s_tx = fma(dx, dx, fma(dy, dy, dz * dz));
+        const double inv_d = rsqrt(s_tx);                                                   // one reciprocal square root
+        const double d_tx = s_tx * inv_d;                                                   // for every channel
+        const double dv = g.ux * dx + g.uy * dy + g.uz * dz;
+#pragma unroll
+        for (int c = 0; c < N; ++c)
+            if (p >= a.first[c] && p < a.first[c] + a.n_used) {
+                const PairChan ch = {a.rc[c], a.fc, a.half_w, a.n_s};
+                tdbp_pair_pixel<SERIES>(a, ch, s_tx, inv_d, d_tx, dv, a.off[c], p, re[c], im[c]);
+            }
+    }
+}
+
+// the tile form's record: 32 + 24 N bytes, padded to a multiple of 16 (80, 112, 128)
+template <int N> struct __attribute__((aligned(16))) MultiTilePulse {
+    double a1, a2;           // 2 Dx, 2 Dy
+    double inv_d0sq, d0;
+    double e0[N], ex[N], ey[N];
+};
+static_assert(sizeof(MultiTilePulse<2>) == 80 && sizeof(MultiTilePulse<3>) == 112 && sizeof(MultiTilePulse<4>) == 128, "whole 16-byte LDS reads");
+
+template <int N> __device__ __forceinline__ MultiTilePulse<N> tdbp_multi_tile_prologue(double dx, double dy, double dz, double ux, double uy, double uz,
+                                                                                     const double* off) {
+    const double s0 = fma(dx, dx, fma(dy, dy, dz * dz));
+    const double inv_d = rsqrt(s0), d0 = s0 * inv_d;
+    const double dv = ux * dx + uy * dy + uz * dz;
+    MultiTilePulse<N> t;
+    t.a1 = 2.0 * dx; t.a2 = 2.0 * dy; t.inv_d0sq = inv_d * inv_d; t.d0 = d0;
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        const double d_rx = sqrt(fma(off[c], off[c] - 2.0 * dv, s0));
+        const double e0 = off[c] * (2.0 * dv - off[c]) / (d0 + d_rx);
+        const double inv = 1.0 / (d0 * d_rx);
+        t.e0[c] = e0;
+        t.ex[c] = (off[c] * d0 * ux - e0 * dx) * inv;
+        t.ey[c] = (off[c] * d0 * uy - e0 * dy) * inv;
+    }
+    return t;
+}
+
+// every thread of the workgroup comes here, dead lanes too: two barriers per batch, as in tdbp_pair_tile_pulses
+template <int N, class A> __device__ __forceinline__ void tdbp_multi_tile_pulses(const A& a, MultiTilePulse<N>* s_tp, double vfx, double vfy, double vfz,
+                                                                               const TdbpTileOffsets& o, int p0, int p1, double (&re)[N], double (&im)[N]) {
+    const double two_inv_ns = 2.0 * a.inv_ns;
+    for (int pb = p0; pb < p1; pb += TP_BATCH) {
+        const int nb = min(TP_BATCH, p1 - pb);
+        __syncthreads();                                   // the previous batch has been consumed
+        if ((int)threadIdx.x < nb) {
+            const PairGeo g = a.geo[pb + threadIdx.x];
+            const double dx = fma(vfx, g.dt, o.xc) - g.px, dy = fma(vfy, g.dt, o.yc) - g.py, dz = vfz * g.dt - g.pz;
+            s_tp[threadIdx.x] = tdbp_multi_tile_prologue<N>(dx, dy, dz, g.ux, g.uy, g.uz, a.off);
+        }
+        __syncthreads();
+        for (int k = 0; k < nb; ++k) {
+            const int p = pb + k;
+            const double d_tx = tdbp_pair_tile_dtx(s_tp[k], o.qx, o.qy, o.q2);
+#pragma unroll
+            for (int c = 0; c < N; ++c)
+                if (p >= a.first[c] && p < a.first[c] + a.n_used) {
+                    const PairChan ch = {a.rc[c], a.fc, a.half_w, a.n_s};
+                    tdbp_pair_tile_pixel(a, ch, s_tp[k], c, d_tx, o.qx, o.qy, two_inv_ns, p, re[c], im[c]);
+                }
         }
     }
 }

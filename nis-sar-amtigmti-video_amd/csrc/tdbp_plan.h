@@ -1,5 +1,5 @@
-// The back-projection plan itself: what tdbp.hip, the focus-velocity search (tdbp_search.hip), the two-receiver pair (tdbp_pair.hip) and
-// the search on the pair per GMTI report (tdbp_pair_search.hip) share and no other unit sees: the plan, the geometry bounds, the scratch a
+// The back-projection plan itself: what tdbp.hip, the focus-velocity search (tdbp_search.hip), the two-receiver pair (tdbp_pair.hip),
+// the search on the pair per GMTI report (tdbp_pair_search.hip) and the N-receiver stack (tdbp_multi.hip) share and no other unit sees: the plan, the geometry bounds, the scratch a
 // unit holds (TdbpScratch; TdbpHypScratch with a hypothesis table) and the kernel arguments they have in common (tdbp_fill_args, tdbp_pair_fill_args).
 #pragma once
 #include <cstring>
@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "tdbp_pixel.hpp"
+#include "tdbp_multi.h"
 #include "tdbp_pair.h"
 #include "tdbp_pair_search.h"
 #include "tdbp_search.h"
@@ -43,6 +44,7 @@ struct Tdbp {
     TdbpSearch* search = nullptr; // scratch of the focus-velocity search (tdbp_search.hip), made by its first call, freed by tdbp_destroy
     TdbpPair* pair = nullptr;     // scratch of the two-receiver pair (tdbp_pair.hip), likewise
     TdbpPairSearch* pair_search = nullptr;   // scratch of the search on the pair (tdbp_pair_search.hip), likewise
+    TdbpMulti* multi = nullptr;   // scratch of the N-receiver stack (tdbp_multi.hip), likewise
 };
 
 #define TCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)

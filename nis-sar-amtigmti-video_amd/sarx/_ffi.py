@@ -395,6 +395,40 @@ TDBP_PAIR_SEARCH_SIGNATURES = {
     "sarx_tdbp_pair_search_route": (_i, [_vp, _P(_i)]),
 }
 
+# include/sarx_tdbp_multi.h: the N-receiver back-projection and the multi-baseline ATI resolver, a thirteenth table bound the same way
+TDBP_MULTI_MAX_RX, TDBP_MULTI_MAX_HALF, TDBP_MULTI_MAX_CANDIDATES, TDBP_MULTI_MAX_DETECTIONS = 4, 4, 129, 16384      # SARX_TDBP_MULTI_MAX_*
+TDBP_MULTI_OK, TDBP_MULTI_NO_CANDIDATE, TDBP_MULTI_ZERO, TDBP_MULTI_OVERFLOW = 0, 1, 2, 3
+
+
+class TdbpMultiParams(C.Structure):
+    """sarx_tdbp_multi_params (64 bytes)"""
+    _fields_ = [("rx_offset_m", C.c_double * 4), ("chirp_centre_s", C.c_double), ("first_pulse", C.c_int32 * 4), ("n_used", C.c_int32),
+                ("n_rx", C.c_int32)]
+
+
+class TdbpMultiResolveParams(C.Structure):
+    """sarx_tdbp_multi_resolve_params (56 bytes)"""
+    _fields_ = [("lag_s", C.c_double * 3), ("wavelength_m", C.c_double), ("v_max_mps", C.c_double), ("n_rx", C.c_int32), ("half", C.c_int32),
+                ("max_detections", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TdbpMultiRecord(C.Structure):
+    """sarx_tdbp_multi_record (64 bytes)"""
+    _fields_ = [("v_los", C.c_double), ("v_coarse", C.c_double), ("cost", C.c_double), ("cost_next", C.c_double), ("phase", C.c_double * 3),
+                ("k", C.c_int32), ("status", C.c_uint32)]
+
+
+_MULTI_ARGS = [_vp, _P(_vp), _vp, _vp, _vp, _d, _vp, _d, _P(TdbpMultiParams), _vp, _vp]
+TDBP_MULTI_SIGNATURES = {
+    "sarx_tdbp_multi_check": (_i, [_i, _P(TdbpMultiParams)]),
+    "sarx_tdbp_multi_dev": (_i, _MULTI_ARGS),
+    "sarx_tdbp_multi_host": (_i, _MULTI_ARGS),
+    "sarx_tdbp_multi_route": (_i, [_vp, _P(_i)]),
+    "sarx_tdbp_multi_scratch": (_i, [_vp, _P(_u64), _P(_u64)]),
+    "sarx_tdbp_multi_resolve_check": (_i, [_P(TdbpMultiResolveParams)]),
+    "sarx_tdbp_multi_resolve_dev": (_i, [_vp, _P(TdbpMultiResolveParams), _vp, _i, _i, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -410,7 +444,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
             list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()) + \
             list(CLUSTER_SIGNATURES.items()) + list(ATIGATE_SIGNATURES.items()) + list(TDBP_SEARCH_SIGNATURES.items()) + \
-            list(TDBP_PAIR_SIGNATURES.items()) + list(TDBP_PAIR_SEARCH_SIGNATURES.items()):
+            list(TDBP_PAIR_SIGNATURES.items()) + list(TDBP_PAIR_SEARCH_SIGNATURES.items()) + list(TDBP_MULTI_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
