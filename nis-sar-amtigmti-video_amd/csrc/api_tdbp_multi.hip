@@ -6,45 +6,6 @@
 
 using namespace sarx;
 
-// what can be said of the parameter block alone; n_pulses < 0: the pulse count is not known yet, the upper end is checked later
-static int multi_params_check(sarx_ctx* c, int n_pulses, const sarx_tdbp_multi_params* k) {
-    if (!k) return fail(c, SARX_ERR_INVALID, "NULL pointer");
-    if (k->n_rx < 2 || k->n_rx > SARX_TDBP_MULTI_MAX_RX) return fail(c, SARX_ERR_INVALID, "n_rx %d must be 2 .. %d", k->n_rx, SARX_TDBP_MULTI_MAX_RX);
-    for (int ch = 0; ch < k->n_rx; ++ch)
-        if (!std::isfinite(k->rx_offset_m[ch])) return fail(c, SARX_ERR_INVALID, "rx_offset_m must be finite");
-    for (int ch = k->n_rx; ch < SARX_TDBP_MULTI_MAX_RX; ++ch)
-        if (!(k->rx_offset_m[ch] == 0.0) || k->first_pulse[ch] != 0)
-            return fail(c, SARX_ERR_INVALID, "unused slot %d of rx_offset_m and first_pulse must be 0", ch);
-    if (!std::isfinite(k->chirp_centre_s)) return fail(c, SARX_ERR_INVALID, "chirp_centre_s must be finite");
-    if (k->n_used < 1) return fail(c, SARX_ERR_INVALID, "n_used %d must be >= 1", k->n_used);
-    for (int ch = 0; ch < k->n_rx; ++ch) {
-        if (k->first_pulse[ch] < 0) return fail(c, SARX_ERR_INVALID, "first_pulse[%d] = %d must be >= 0", ch, k->first_pulse[ch]);
-        if (n_pulses >= 0 && (long long)k->first_pulse[ch] + k->n_used > n_pulses)
-            return fail(c, SARX_ERR_INVALID, "channel %d: pulses %d .. %lld lie outside [0, %d]", ch, k->first_pulse[ch],
-                        (long long)k->first_pulse[ch] + k->n_used, n_pulses);
-    }
-    return SARX_OK;
-}
-
-// The order of api_tdbp_pair.hip: what needs no plan first, the plan next, last what needs the plan's pulse count.  The channel
-// pointers are read only once n_rx is known to be good.
-static int multi_check(sarx_tdbp_plan* p, bool pointers_ok, const void* const* raw, const double* vel_tx, const double* vel_focus, double scene_size,
-                       const sarx_tdbp_multi_params* k, const void* img128, const void* img64, sarx_ctx** c) {
-    *c = tdbp_plan_live(p) ? p->ctx : nullptr;
-    if (!pointers_ok) return fail(*c, SARX_ERR_INVALID, "NULL pointer");
-    if (!img128 && !img64) return fail(*c, SARX_ERR_INVALID, "both outputs are NULL");
-    if (((uintptr_t)img128 & 15) || ((uintptr_t)img64 & 7)) return fail(*c, SARX_ERR_INVALID, "misaligned images128 (16) or images64 (8)");
-    for (int i = 0; i < 3; ++i)
-        if (!std::isfinite(vel_focus[i])) return fail(*c, SARX_ERR_INVALID, "vel_focus has a non-finite component");
-    if (const int rc = tdbp_scene_check(*c, scene_size)) return rc;
-    if (const int rc = multi_params_check(*c, -1, k)) return rc;
-    for (int ch = 0; ch < k->n_rx; ++ch)
-        if (!raw[ch]) return fail(*c, SARX_ERR_INVALID, "NULL pointer for the raw pulses of channel %d", ch);
-    if (const int rc = tdbp_plan_usable(p, c)) return rc;
-    if (const int rc = multi_params_check(*c, p->n_p, k)) return rc;
-    return tdbp_vel_tx_check(*c, vel_tx, p->n_p);
-}
-
 static int resolve_check(sarx_ctx* c, const sarx_tdbp_multi_resolve_params* p) {
     if (!p) return fail(c, SARX_ERR_INVALID, "resolver params is NULL");
     if (p->n_rx < 2 || p->n_rx > SARX_TDBP_MULTI_MAX_RX) return fail(c, SARX_ERR_INVALID, "n_rx %d must be 2 .. %d", p->n_rx, SARX_TDBP_MULTI_MAX_RX);
@@ -75,14 +36,14 @@ extern "C" {
 
 int sarx_tdbp_multi_check(int n_pulses, const sarx_tdbp_multi_params* params) {
     if (n_pulses < 1) return fail(nullptr, SARX_ERR_INVALID, "n_pulses %d must be >= 1", n_pulses);
-    return multi_params_check(nullptr, n_pulses, params);
+    return tdbp_multi_params_check(nullptr, n_pulses, params);
 }
 
 int sarx_tdbp_multi_dev(sarx_tdbp_plan* p, const void* const* d_raw, const double* pos_tx, const double* vel_tx, const double* t_pulses,
                         double t_start, const double* vel_focus, double scene_size, const sarx_tdbp_multi_params* params,
                         void* d_images128, void* d_images64) {
     sarx_ctx* c = nullptr;
-    const int rc = multi_check(p, d_raw && pos_tx && vel_tx && t_pulses && vel_focus && params, d_raw, vel_tx, vel_focus, scene_size, params,
+    const int rc = tdbp_rx_check(p, d_raw && pos_tx && vel_tx && t_pulses && vel_focus && params, d_raw, vel_tx, vel_focus, scene_size, params,
                                d_images128, d_images64, &c);
     if (rc != SARX_OK) return rc;
     return guarded(c, [&] {
@@ -96,7 +57,7 @@ int sarx_tdbp_multi_host(sarx_tdbp_plan* p, const void* const* raw, const double
                          double t_start, const double* vel_focus, double scene_size, const sarx_tdbp_multi_params* params,
                          void* images128, void* images64) {
     sarx_ctx* c = nullptr;
-    const int rc = multi_check(p, raw && pos_tx && vel_tx && t_pulses && vel_focus && params, raw, vel_tx, vel_focus, scene_size, params,
+    const int rc = tdbp_rx_check(p, raw && pos_tx && vel_tx && t_pulses && vel_focus && params, raw, vel_tx, vel_focus, scene_size, params,
                                images128, images64, &c);
     if (rc != SARX_OK) return rc;
     return guarded(c, [&] {

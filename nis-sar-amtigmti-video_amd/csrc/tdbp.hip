@@ -107,9 +107,9 @@ void tdbp_destroy(Tdbp* t) {
     }
     hipFree(t->part); hipFree(t->img);
     tdbp_search_free(t->search);
-    tdbp_pair_free(t->pair);
+    tdbp_rx_free(t->pair);
     tdbp_pair_search_free(t->pair_search);
-    tdbp_multi_free(t->multi);
+    tdbp_rx_free(t->multi);
     delete t;
 }
 

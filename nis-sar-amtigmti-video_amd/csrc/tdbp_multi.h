@@ -6,7 +6,7 @@
 #include "tdbp.h"
 
 namespace sarx {
-struct TdbpMulti;                                       // the scratch, owned by the plan
+struct TdbpRx;                                          // the scratch of a receiver stack (tdbp_plan.h), owned by the plan
 // raw: n_rx device pointers [n_p][n_s]; pos, vel: host [n_p][3] (no zero vel row); t_pulses: host [n_p]; vel_focus: host [3]; prm:
 // checked by the caller against n_p.  chunks: pulse chunks, 0 = chosen here.  d_img128: device complex128 [n_rx][ny][nx] or NULL;
 // d_img64: device complex64 [n_rx][ny][nx] or NULL.
@@ -18,7 +18,6 @@ int tdbp_multi_route(const Tdbp* t);                    // 1 tile form, 0 exact 
 hipError_t tdbp_multi_staging(Tdbp* t, int n_rx, float2** d_raw, double2** d_img128, float2** d_img64);
 // bytes the scratch holds on the device and a sum over its buffers' addresses (0, 0 before any multi call)
 void tdbp_multi_held(const Tdbp* t, uint64_t* bytes, uint64_t* id);
-void tdbp_multi_free(TdbpMulti* s);
 
 struct MultiResolveArgs {
     sarx_tdbp_multi_resolve_params p;

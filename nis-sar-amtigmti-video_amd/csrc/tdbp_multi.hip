@@ -1,8 +1,10 @@
 // N-receiver back-projection and the multi-baseline ATI resolver (include/sarx_tdbp_multi.h).
 //
-// The stack: n_rx = 2, 3 or 4 receive channels imaged onto one ground grid in one enqueue, the steps of tdbp_pair.hip with N channels:
+// The stack: n_rx = 2, 3 or 4 receive channels imaged onto one ground grid in one enqueue.  The two-receiver pair (tdbp_pair.hip,
+// DESIGN.md 4.18) is its n_rx = 2 case on a scratch of its own:
 //   1 range compression, once per channel, over ONE sample window that bounds what any channel can touch (tdbp_pair_bounds with the
-//     largest |offset|).  Channel 0 lands in the plan's rc buffer, channels 1 .. 3 in the scratch's.
+//     largest |offset|: a bound, not an estimate).  Channel 0 lands in the plan's rc buffer, channels 1 .. 3 in the scratch's:
+//     tdbp_range_compress takes its destination.
 //   2 back-projection: one thread per pixel carries all N channels.  Per pulse the pixel moved with the focus velocity, the vector to
 //     the transmitter, d_tx, its reciprocal square root and d . v^ are computed once; each channel adds only its receive leg, its
 //     interpolation coordinate and its sample.  The loop runs over the UNION of the channels' pulse ranges; a channel accumulates only
@@ -10,8 +12,9 @@
 //   3 one reduce launch over the N channels: chunks summed in chunk order, written as complex128 and / or complex64.  No atomics.
 // Two forms of the geometry, templated on N: the exact one (tdbp_multi_kernel<N, SERIES>) and the tile-expanded one
 // (tdbp_multi_tile_kernel<N>: a 256-pulse batch of 32 + 24 N byte records in LDS, 20, 28 and 32 KiB), taken when tdbp_tile_ok and
-// the pair's bound with the largest |offset| hold.  The pulse loops are tdbp_pixel.hpp's; every channel's statements are the pair's,
-// the chunks are picked as the pair picks them, so n_rx = 2 gives the pair's bits.
+// the receivers' bound with the largest |offset| hold.  Same pulse order per pixel, same fp64 accumulation.  The pulse loops are
+// tdbp_pixel.hpp's (tdbp_multi_pulses, tdbp_multi_tile_pulses): the search on the pair (tdbp_pair_search.hip) runs them at N = 2.
+// Pulse chunks: tdbp_pick_chunks (tdbp.hip); pulse table, channel buffers, staging and partial images: a TdbpRx (tdbp_plan.h).
 //
 // The resolver (tdbp_multi_resolve_kernel): one lane per report of a GMTI slot, the count read from the slot's header on the device.
 #include <hip/hip_runtime.h>
@@ -27,21 +30,12 @@ namespace sarx {
 static_assert(sizeof(sarx_tdbp_multi_params) == 64, "sarx_tdbp_multi_params is 64 bytes");
 static_assert(sizeof(sarx_tdbp_multi_resolve_params) == 56, "sarx_tdbp_multi_resolve_params is 56 bytes");
 static_assert(sizeof(sarx_tdbp_multi_record) == 64, "sarx_tdbp_multi_record is 64 bytes");
-constexpr int MAX_RX = SARX_TDBP_MULTI_MAX_RX;
+static_assert(MAX_RX == SARX_TDBP_MULTI_MAX_RX, "RxArgs holds SARX_TDBP_MULTI_MAX_RX channels");
 
-struct MultiArgs {
-    const cf* rc[MAX_RX];    // [n_p][n_s] range-compressed pulses of channel c
-    double fc;               // what tdbp_sample reads beside rc, the same for every channel
-    float half_w;
-    int n_s;
-    const PairGeo* geo;
+struct MultiArgs : RxArgs {
     const double *xax, *yax;
     double2* part;           // [n_rx][chunks][ny*nx]
     double vfx, vfy, vfz;
-    double off[MAX_RX];
-    double inv_c, fs, t_start, chirp_centre, inv_ns;
-    int first[MAX_RX], n_used;   // channel c: pulses [first[c], first[c] + n_used)
-    int u0, u1;              // their union
     int nx, ny, per_chunk, chunks;
 };
 
@@ -62,6 +56,7 @@ template <int N, bool SERIES> __global__ __launch_bounds__(256) void tdbp_multi_
     store_partial<N>(a, px, re, im);
 }
 
+// the tile form (tdbp_pixel.hpp): one lane per pulse fills the batch's records, then every pixel walks them
 template <int N> __global__ __launch_bounds__(256) void tdbp_multi_tile_kernel(MultiArgs a) {
     __shared__ MultiTilePulse<N> s_tp[TP_BATCH];
     const TdbpPix px = tdbp_pix(a.nx, a.ny);
@@ -83,14 +78,7 @@ __global__ __launch_bounds__(256) void tdbp_multi_reduce_kernel(const double2* p
     }
 }
 
-struct TdbpMulti : TdbpScratch {                           // the table holds PairGeo
-    cf* rc[MAX_RX - 1] = {};                               // [n_p][n_s] range-compressed pulses of channels 1 .. 3, made when first used
-    float2* raw[MAX_RX - 1] = {};                          // staging of the host entry point, likewise
-    double2* img128 = nullptr;                             // [MAX_RX][ny*nx]
-    float2* img64 = nullptr;
-};
-
-void tdbp_multi_free(TdbpMulti* s) {
+void tdbp_rx_free(TdbpRx* s) {
     if (!s) return;
     tdbp_scratch_free(s);
     for (int c = 0; c < MAX_RX - 1; ++c) { hipFree(s->rc[c]); hipFree(s->raw[c]); }
@@ -98,16 +86,17 @@ void tdbp_multi_free(TdbpMulti* s) {
     delete s;
 }
 
-static hipError_t multi_scratch(Tdbp* t, int n_rx, TdbpMulti** out) {
-    if (!t->multi) {
-        TdbpMulti* s = new TdbpMulti();
+hipError_t tdbp_rx_scratch(Tdbp* t, TdbpRx*& inst, int cap, int n_rx, TdbpRx** out) {
+    if (!inst) {
+        TdbpRx* s = new TdbpRx();
+        s->cap = cap;
         const hipError_t e = tdbp_scratch_init(s, t->n_p, sizeof(PairGeo));
-        if (e != hipSuccess) { tdbp_multi_free(s); return e; }
-        t->multi = s;
+        if (e != hipSuccess) { tdbp_rx_free(s); return e; }
+        inst = s;
     }
     for (int c = 0; c < n_rx - 1; ++c)
-        if (!t->multi->rc[c]) TCK(hipMalloc(&t->multi->rc[c], (size_t)t->n_p * t->n_s * sizeof(cf)));
-    *out = t->multi;
+        if (!inst->rc[c]) TCK(hipMalloc(&inst->rc[c], (size_t)t->n_p * t->n_s * sizeof(cf)));
+    *out = inst;
     return hipSuccess;
 }
 
@@ -117,51 +106,38 @@ template <int N> static void launch_multi(const MultiArgs& a, bool tile, bool se
     else hipLaunchKernelGGL((tdbp_multi_kernel<N, false>), grid, dim3(256), 0, st, a);
 }
 
-hipError_t tdbp_multi(Tdbp* t, const float2* const* raw, const double* pos, const double* vel, const double* t_pulses, double t_start,
-                      const double* vel_focus, double scene_size, const sarx_tdbp_multi_params* prm, int chunks, double2* d_img128,
-                      float2* d_img64, hipStream_t st) {
+hipError_t tdbp_rx(Tdbp* t, TdbpRx*& inst, int cap, const float2* const* raw, const double* pos, const double* vel, const double* t_pulses,
+                   double t_start, const double* vel_focus, double scene_size, const sarx_tdbp_multi_params* prm, int chunks,
+                   double2* d_img128, float2* d_img64, hipStream_t st) {
     const int n_rx = prm->n_rx, n_p = t->n_p;
-    TdbpMulti* s = nullptr;
-    TCK(multi_scratch(t, n_rx, &s));
+    TdbpRx* s = nullptr;
+    TCK(tdbp_rx_scratch(t, inst, cap, n_rx, &s));
     MultiArgs a{};
-    // the union of the channels' pulse ranges, and the pair's bounds taken with the largest |offset|: tdbp_pair_bounds reads nothing
-    // else of the offsets, so one sample window, one series test and one tile test hold for every channel
-    sarx_tdbp_pair_params widest{};
-    widest.chirp_centre_s = prm->chirp_centre_s;
-    a.u0 = prm->first_pulse[0]; a.u1 = prm->first_pulse[0];
-    for (int c = 0; c < n_rx; ++c) {
-        if (fabs(prm->rx_offset_m[c]) > widest.rx_offset_m[0]) widest.rx_offset_m[0] = widest.rx_offset_m[1] = fabs(prm->rx_offset_m[c]);
-        if (prm->first_pulse[c] < a.u0) a.u0 = prm->first_pulse[c];
-        if (prm->first_pulse[c] > a.u1) a.u1 = prm->first_pulse[c];
-    }
-    a.u1 += prm->n_used;
+    tdbp_rx_fill_args(t, t_start, prm, a);
     std::vector<PulseGeo> geo;
     tdbp_pulse_table(t, pos, t_pulses, geo);               // position and dt = t_pulse - mean over all n_p
     int lo = 0, hi = t->n_s;
     bool series = true, tile = false;
-    tdbp_pair_bounds(t, geo, a.u0, a.u1, vel_focus, t_start, scene_size, &widest, &lo, &hi, &series, &tile);
+    tdbp_pair_bounds(t, geo, a.u0, a.u1, vel_focus, t_start, scene_size, tdbp_rx_off_max(a, n_rx), a.chirp_centre, &lo, &hi, &series, &tile);
     tile = tile && tdbp_tile_ok(t, geo, vel_focus, scene_size);   // the d_tx series, and the switch SARX_TDBP_TILE=0
     if (t->full_rc) { lo = 0; hi = t->n_s; }
-    for (int c = 0; c < n_rx; ++c) TCK(tdbp_range_compress(t, raw[c], c ? s->rc[c - 1] : t->rc, lo, hi, st));
+    for (int c = 0; c < n_rx; ++c) {
+        cf* const dst = c ? s->rc[c - 1] : t->rc;          // the same launches, the channel's destination
+        a.rc[c] = dst;
+        TCK(tdbp_range_compress(t, raw[c], dst, lo, hi, st));
+    }
     TCK(tdbp_scratch_upload(s, st, [&](void* staging) {
         tdbp_pair_table((PairGeo*)staging, geo, vel, n_p);
         return hipSuccess;
     }));
     TCK(tdbp_ensure_axes(t, scene_size, st));
-    // pulse chunks over the union's pulses, one chunk launching tiles workgroups: the pair's choice
+    // pulse chunks over the union's pulses, one chunk launching tiles workgroups
     const int tiles = ((t->nx + 15) / 16) * ((t->ny + 15) / 16);
     int per_chunk = 0;
     chunks = tdbp_pick_chunks(tiles, 1, a.u1 - a.u0, chunks, &per_chunk);
     const size_t n_pix = (size_t)t->nx * t->ny;
     TCK(grow(&s->part, &s->part_cap, (size_t)n_rx * chunks * n_pix));
-    for (int c = 0; c < n_rx; ++c) {
-        a.rc[c] = c ? s->rc[c - 1] : t->rc;
-        a.off[c] = prm->rx_offset_m[c]; a.first[c] = prm->first_pulse[c];
-    }
-    a.n_used = prm->n_used;
-    a.fc = t->k.fc; a.half_w = (float)t->n_s / 2.0f; a.n_s = t->n_s;
     a.geo = (const PairGeo*)s->geo; a.xax = t->xax; a.yax = t->yax;
-    a.inv_c = 1.0 / t->k.c; a.fs = t->k.fs; a.t_start = t_start; a.chirp_centre = prm->chirp_centre_s; a.inv_ns = 1.0 / (double)t->n_s;
     a.part = s->part;
     a.vfx = vel_focus[0]; a.vfy = vel_focus[1]; a.vfz = vel_focus[2];
     a.nx = t->nx; a.ny = t->ny; a.per_chunk = per_chunk; a.chunks = chunks;
@@ -175,33 +151,44 @@ hipError_t tdbp_multi(Tdbp* t, const float2* const* raw, const double* pos, cons
     return hipGetLastError();
 }
 
+hipError_t tdbp_multi(Tdbp* t, const float2* const* raw, const double* pos, const double* vel, const double* t_pulses, double t_start,
+                      const double* vel_focus, double scene_size, const sarx_tdbp_multi_params* prm, int chunks, double2* d_img128,
+                      float2* d_img64, hipStream_t st) {
+    return tdbp_rx(t, t->multi, MAX_RX, raw, pos, vel, t_pulses, t_start, vel_focus, scene_size, prm, chunks, d_img128, d_img64, st);
+}
+
 int tdbp_multi_route(const Tdbp* t) { return t->multi ? t->multi->route : -1; }
 
-void tdbp_multi_held(const Tdbp* t, uint64_t* bytes, uint64_t* id) {
+void tdbp_rx_held(const Tdbp* t, const TdbpRx* s, uint64_t* bytes, uint64_t* id) {
     *bytes = 0; *id = 0;
-    const TdbpMulti* s = t->multi;
     if (!s) return;
     const size_t n = (size_t)t->n_p * t->n_s, n_pix = (size_t)t->nx * t->ny;
     const auto held = [&](const void* p, size_t b) { if (p) { *bytes += b; *id += (uint64_t)(uintptr_t)p; } };
     held(s->geo, s->bytes);
     held(s->part, s->part_cap * sizeof(double2));
     for (int c = 0; c < MAX_RX - 1; ++c) { held(s->rc[c], n * sizeof(cf)); held(s->raw[c], n * sizeof(float2)); }
-    held(s->img128, MAX_RX * n_pix * sizeof(double2));
-    held(s->img64, MAX_RX * n_pix * sizeof(float2));
+    held(s->img128, s->cap * n_pix * sizeof(double2));
+    held(s->img64, s->cap * n_pix * sizeof(float2));
 }
 
-hipError_t tdbp_multi_staging(Tdbp* t, int n_rx, float2** d_raw, double2** d_img128, float2** d_img64) {
-    TdbpMulti* s = nullptr;
-    TCK(multi_scratch(t, n_rx, &s));
+void tdbp_multi_held(const Tdbp* t, uint64_t* bytes, uint64_t* id) { tdbp_rx_held(t, t->multi, bytes, id); }
+
+hipError_t tdbp_rx_staging(Tdbp* t, TdbpRx*& inst, int cap, int n_rx, float2** d_raw, double2** d_img128, float2** d_img64) {
+    TdbpRx* s = nullptr;
+    TCK(tdbp_rx_scratch(t, inst, cap, n_rx, &s));
     const size_t n_pix = (size_t)t->nx * t->ny;
     for (int c = 0; c < n_rx - 1; ++c) {
         if (!s->raw[c]) TCK(hipMalloc(&s->raw[c], (size_t)t->n_p * t->n_s * sizeof(float2)));
         d_raw[c] = s->raw[c];
     }
-    if (!s->img128) TCK(hipMalloc(&s->img128, MAX_RX * n_pix * sizeof(double2)));
-    if (!s->img64) TCK(hipMalloc(&s->img64, MAX_RX * n_pix * sizeof(float2)));
+    if (!s->img128) TCK(hipMalloc(&s->img128, s->cap * n_pix * sizeof(double2)));
+    if (!s->img64) TCK(hipMalloc(&s->img64, s->cap * n_pix * sizeof(float2)));
     *d_img128 = s->img128; *d_img64 = s->img64;
     return hipSuccess;
+}
+
+hipError_t tdbp_multi_staging(Tdbp* t, int n_rx, float2** d_raw, double2** d_img128, float2** d_img64) {
+    return tdbp_rx_staging(t, t->multi, MAX_RX, n_rx, d_raw, d_img128, d_img64);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@
 //     bound (tdbp_pair_bounds) over the whole grid - the chips are not known on the host.  Channel 0 lands in the plan's rc buffer,
 //     channel 1 in the pair scratch's.
 //   2 back-projection: grid (tiles of the chip) x (report * n_hyp + hypothesis) x (pulse chunk), one thread per chip pixel carrying
-//     BOTH channels through the pulse loops tdbp_pair.hip's kernels run (tdbp_pair_pulses, tdbp_pair_tile_pulses of tdbp_pixel.hpp).
+//     BOTH channels through the pulse loops tdbp_multi.hip's kernels run, at N = 2 (tdbp_multi_pulses, tdbp_multi_tile_pulses of tdbp_pixel.hpp).
 //     A workgroup reads the slot's header and its report: past the count, on an overflowed slot or with the report outside the grid
 //     it leaves at once (before any barrier; the test is workgroup-uniform).  Partial chips [max_det][n_hyp][chunks][2][chip_y * chip_x].
 //     The exact form (tdbp_pair_search_kernel) and the one expanded about the reference pixel of each 16 x 16 tile OF THE CHIP
@@ -36,9 +36,7 @@ static_assert(sizeof(sarx_tdbp_pair_search_params) == 16, "sarx_tdbp_pair_search
 static_assert(sizeof(sarx_tdbp_pair_search_best) == 80, "sarx_tdbp_pair_search_best is 80 bytes");
 static_assert(sizeof(sarx_tdbp_search_record) == 32, "sarx_tdbp_search_record is 32 bytes");
 
-struct PairSearchArgs {
-    PairChan ch[2];
-    const PairGeo* geo;
+struct PairSearchArgs : RxArgs {     // channels 0 and 1
     const double* hyps;              // [n_hyp][3]
     const double *xax, *yax;
     const sarx_gmti_report* rep;
@@ -47,10 +45,6 @@ struct PairSearchArgs {
     sarx_tdbp_search_record* rec;    // [max_det][n_hyp]
     sarx_tdbp_pair_search_best* best;   // [max_det]
     double2* chips;                  // [max_det][n_hyp][2][chip_y * chip_x] or NULL
-    double off[2];
-    double inv_c, fs, t_start, chirp_centre, inv_ns;
-    int first[2], n_used;            // channel c: pulses [first[c], first[c] + n_used)
-    int u0, u1;                      // their union
     int nx, ny, chip_x, chip_y, n_hyp, max_det, source, per_chunk, chunks;
 };
 
@@ -68,12 +62,12 @@ __device__ __forceinline__ int chip_of(const PairSearchArgs& a, int r, int& x0, 
 }
 
 // the partial chip of channel ch of this workgroup's (report, hypothesis) = blockIdx.y and chunk = blockIdx.z
-__device__ __forceinline__ void store_partial(const PairSearchArgs& a, const TdbpPix& px, double re0, double im0, double re1, double im1) {
+__device__ __forceinline__ void store_partial(const PairSearchArgs& a, const TdbpPix& px, const double (&re)[2], const double (&im)[2]) {
     if (!px.live) return;
     const size_t n_chip = (size_t)a.chip_x * a.chip_y;
     const size_t at = ((size_t)blockIdx.y * a.chunks + blockIdx.z) * 2 * n_chip + (size_t)px.iy * a.chip_x + px.ix;
-    a.part[at] = make_double2(re0, im0);
-    a.part[at + n_chip] = make_double2(re1, im1);
+    a.part[at] = make_double2(re[0], im[0]);
+    a.part[at + n_chip] = make_double2(re[1], im[1]);
 }
 
 template <bool SERIES> __global__ __launch_bounds__(256) void tdbp_pair_search_kernel(PairSearchArgs a) {
@@ -84,14 +78,14 @@ template <bool SERIES> __global__ __launch_bounds__(256) void tdbp_pair_search_k
     const double gx0 = a.xax[x0 + (px.live ? px.ix : 0)], gy0 = a.yax[y0 + (px.live ? px.iy : 0)];
     const double vfx = a.hyps[3 * h], vfy = a.hyps[3 * h + 1], vfz = a.hyps[3 * h + 2];
     const int p0 = a.u0 + blockIdx.z * a.per_chunk, p1 = min(a.u1, p0 + a.per_chunk);
-    double re0 = 0.0, im0 = 0.0, re1 = 0.0, im1 = 0.0;
-    tdbp_pair_pulses<SERIES>(a, vfx, vfy, vfz, gx0, gy0, p0, p1, re0, im0, re1, im1);
-    store_partial(a, px, re0, im0, re1, im1);
+    double re[2] = {}, im[2] = {};
+    tdbp_multi_pulses<2, SERIES>(a, vfx, vfy, vfz, gx0, gy0, p0, p1, re, im);
+    store_partial(a, px, re, im);
 }
 
 // the tile form on the chip's own tiles: the axis tables shifted to the chip's corner, the chip's extent as the grid
 __global__ __launch_bounds__(256) void tdbp_pair_search_tile_kernel(PairSearchArgs a) {
-    __shared__ PairTilePulse s_tp[TP_BATCH];
+    __shared__ MultiTilePulse<2> s_tp[TP_BATCH];
     const int r = blockIdx.y / a.n_hyp, h = blockIdx.y - r * a.n_hyp;
     int x0 = 0, y0 = 0;
     if (chip_of(a, r, x0, y0) != CHIP_RUN) return;        // the whole workgroup, before the first barrier
@@ -99,9 +93,9 @@ __global__ __launch_bounds__(256) void tdbp_pair_search_tile_kernel(PairSearchAr
     const TdbpTileOffsets o = tdbp_tile_offsets(a.xax + x0, a.yax + y0, px, a.chip_x, a.chip_y);
     const double vfx = a.hyps[3 * h], vfy = a.hyps[3 * h + 1], vfz = a.hyps[3 * h + 2];
     const int p0 = a.u0 + blockIdx.z * a.per_chunk, p1 = min(a.u1, p0 + a.per_chunk);
-    double re0 = 0.0, im0 = 0.0, re1 = 0.0, im1 = 0.0;
-    tdbp_pair_tile_pulses(a, s_tp, vfx, vfy, vfz, o, p0, p1, re0, im0, re1, im1);
-    store_partial(a, px, re0, im0, re1, im1);
+    double re[2] = {}, im[2] = {};
+    tdbp_multi_tile_pulses<2>(a, s_tp, vfx, vfy, vfz, o, p0, p1, re, im);
+    store_partial(a, px, re, im);
 }
 
 static constexpr int PM = 256;
@@ -245,8 +239,11 @@ hipError_t tdbp_pair_search(Tdbp* t, const float2* raw0, const float2* raw1, con
                             const sarx_tdbp_pair_search_params* sp, int chunks, sarx_tdbp_search_record* d_records,
                             sarx_tdbp_pair_search_best* d_best, double2* d_chips, std::string* why, hipStream_t st) {
     const int n_p = t->n_p, n_hyp = sp->n_hyp;
-    int u0 = 0, u1 = 0;
-    tdbp_pair_union(prm, &u0, &u1);
+    const sarx_tdbp_multi_params m = tdbp_pair_as_multi(*prm);
+    PairSearchArgs a{};
+    tdbp_rx_fill_args(t, t_start, &m, a);
+    const int u0 = a.u0, u1 = a.u1;
+    const double off_max = tdbp_rx_off_max(a, 2);
     // pulse chunks over the union's pulses, one chunk launching tiles x max_det x n_hyp workgroups; the partial chips must fit the cap
     const int tiles = ((sp->chip_x + 15) / 16) * ((sp->chip_y + 15) / 16);
     const size_t n_chip = (size_t)sp->chip_x * sp->chip_y;
@@ -276,7 +273,7 @@ hipError_t tdbp_pair_search(Tdbp* t, const float2* raw0, const float2* raw1, con
         const double* vf = vel_hyps + 3 * h;
         int l = 0, u = t->n_s;
         bool ser = true, til = false;
-        tdbp_pair_bounds(t, geo, u0, u1, vf, t_start, scene_size, prm, &l, &u, &ser, &til);
+        tdbp_pair_bounds(t, geo, u0, u1, vf, t_start, scene_size, off_max, a.chirp_centre, &l, &u, &ser, &til);
         if (u > l) { if (l < lo) lo = l; if (u > hi) hi = u; }
         series = series && ser;
         if (tile) tile = til && tdbp_tile_ok(t, geo, vf, scene_size);   // the d_tx series, and the switch SARX_TDBP_TILE=0
@@ -287,8 +284,7 @@ hipError_t tdbp_pair_search(Tdbp* t, const float2* raw0, const float2* raw1, con
     TCK(tdbp_hyp_upload(s, vel_hyps, n_hyp, st, [&](void* staging) { tdbp_pair_table((PairGeo*)staging, geo, vel, n_p); }));
     TCK(tdbp_ensure_axes(t, scene_size, st));
     TCK(grow(&s->part, &s->part_cap, per_chunk_bytes / sizeof(double2) * n_chunks));
-    PairSearchArgs a{};
-    tdbp_pair_fill_args(t, s, rc1, t_start, prm, a);
+    a.rc[0] = t->rc; a.rc[1] = rc1; a.geo = (const PairGeo*)s->geo; a.xax = t->xax; a.yax = t->yax;
     a.hyps = s->hyps;
     a.rep = d_reports; a.hdr = d_header; a.part = s->part; a.rec = d_records; a.best = d_best; a.chips = d_chips;
     a.nx = t->nx; a.ny = t->ny; a.chip_x = sp->chip_x; a.chip_y = sp->chip_y; a.n_hyp = n_hyp; a.max_det = max_det; a.source = sp->source;

@@ -1,10 +1,10 @@
 // One pixel and pulse of the time-domain back-projection (sar_batch_sim.py:205-232), stated once for the focus kernels of tdbp.hip,
-// the focus-velocity search kernels of tdbp_search.hip, the two-receiver kernels of tdbp_pair.hip and their search per GMTI report
-// (tdbp_pair_search.hip), with what stands around it in every one of them: the tile and pixel coordinates of a thread (tdbp_pix), a
+// the focus-velocity search kernels of tdbp_search.hip, the N-receiver kernels of tdbp_multi.hip and the two-receiver search per GMTI
+// report (tdbp_pair_search.hip), with what stands around it in every one of them: the tile and pixel coordinates of a thread (tdbp_pix), a
 // pixel's offset from its tile's reference pixel (tdbp_tile_offsets) and the fixed-order sum of a pixel's chunks (tdbp_sum_chunks).
 // A single-channel kernel keeps only where the focus velocity v_f and w = v_plat - v_f come from, the batch loop of the tile form and the
-// place of its partial image; the pair's whole pulse loops are here (tdbp_pair_pulses, tdbp_pair_tile_pulses) for its four kernels, and
-// beside them the same loops for N = 2, 3 or 4 receivers (tdbp_multi_pulses, tdbp_multi_tile_pulses) for the kernels of tdbp_multi.hip.
+// place of its partial image; the whole pulse loops of N = 2, 3 or 4 receivers are here (tdbp_multi_pulses, tdbp_multi_tile_pulses), for
+// the kernels of tdbp_multi.hip and, at N = 2, for the pair and the kernels of its search.
 // Every statement groups its operands as the reference parity (1e-4) was measured with: -ffp-contract=on fuses inside a statement
 // only, so splitting or merging one changes bits.
 #pragma once
@@ -145,15 +145,17 @@ template <class A> __device__ __forceinline__ void tdbp_tile_pixel(const A& c, c
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// The two-receiver pair (tdbp_pair.hip): receiver c rides at pos_tx + off_c v^ (sar_ati_dcpa_sim_csa.py:145-159),
-// there is no stop-and-go receiver and no t_shift.  d, s_tx, inv_d, d_tx are the transmit leg, computed once per pixel and pulse
-// for both channels; dv = d . v^.
+// N = 2, 3 or 4 receivers (tdbp_multi.hip; N = 2 is the two-receiver pair and its search, 4.19): receiver c
+// rides at pos_tx + off_c v^ (sar_ati_dcpa_sim_csa.py:145-159), there is no stop-and-go receiver and no t_shift.  d, s_tx, inv_d, d_tx
+// are the transmit leg, computed once per pixel and pulse for every channel; dv = d . v^.
 //   d_rx^2 = d_tx^2 - 2 off dv + off^2 = d_tx^2 (1 - e),  e = off (2 dv - off) / d_tx^2,  |e| <= 2 |off| / d_tx + (off / d_tx)^2.
 // SERIES: sqrt(1 - e) by the series of tdbp_exact_pixel; its first omitted term is 7 e^5 / 256, and the launcher takes this form
-// only when 7 e_max^5 / 256 * d_max < 1e-9 m over all pulses (tdbp_pair_series_ok: e ~ 5e-6 at the reference geometry, where the
+// only when 7 e_max^5 / 256 * d_max < 1e-9 m over all pulses (tdbp_pair_bounds: e ~ 5e-6 at the reference geometry, where the
 // term is 1e-23 m); otherwise the plain square root runs.
-// A: the kernel's arguments (inv_c, t_start, chirp_centre, fs, inv_ns); PairChan: what tdbp_sample reads of one channel.
+// A: the kernel's arguments, an RxArgs; PairChan: what tdbp_sample reads of one channel, made of the arguments per channel.
 // ------------------------------------------------------------------------------------------------------------
+static constexpr int MAX_RX = 4;
+
 struct PairChan {
     const cf* rc;            // [n_p][n_s] range-compressed pulses of this channel
     double fc;
@@ -161,10 +163,25 @@ struct PairChan {
     int n_s;
 };
 
-struct PairGeo {             // the pair's table: one 64-byte record per pulse, read with scalar loads
+struct PairGeo {             // the receivers' table: one 64-byte record per pulse, read with scalar loads
     double px, py, pz;       // transmitter
     double ux, uy, uz;       // v^ = vel_tx / |vel_tx|
     double dt, pad;
+};
+
+// What the loops below read of a kernel's arguments: MultiArgs (tdbp_multi.hip) and PairSearchArgs (tdbp_pair_search.hip) derive from
+// it, tdbp_rx_fill_args (tdbp_plan.h) sets it.  The order of the fields is kept as it is on purpose: with off[] ahead of the five
+// constants the compiler gives the N = 2 tile kernel another schedule and register count.
+struct RxArgs {
+    const cf* rc[MAX_RX];    // [n_p][n_s] range-compressed pulses of channel c
+    double fc;               // what tdbp_sample reads beside rc, the same for every channel
+    float half_w;
+    int n_s;
+    const PairGeo* geo;
+    double inv_c, fs, t_start, chirp_centre, inv_ns;
+    double off[MAX_RX];
+    int first[MAX_RX], n_used;   // channel c: pulses [first[c], first[c] + n_used)
+    int u0, u1;              // their union
 };
 
 template <bool SERIES, class A> __device__ __forceinline__ void tdbp_pair_pixel(const A& c, const PairChan& ch, double s_tx, double inv_d,
@@ -184,113 +201,8 @@ template <bool SERIES, class A> __device__ __forceinline__ void tdbp_pair_pixel(
     tdbp_sample(ch, xn, tau, p, acc_re, acc_im);
 }
 
-// The pulses [p0, p1) of one pixel at (gx0, gy0) under the focus velocity vf, both channels.  A: PairArgs, PairSearchArgs; read here
-// beside what tdbp_pair_pixel reads: geo, ch[2], off[2], first[2], n_used - the fields tdbp_pair_fill_args (tdbp_plan.h) sets.  A
-// channel accumulates only inside its own pulse range (a wave-uniform test).
-template <bool SERIES, class A> __device__ __forceinline__ void tdbp_pair_pulses(const A& a, double vfx, double vfy, double vfz, double gx0, double gy0,
-                                                                               int p0, int p1, double& re0, double& im0, double& re1, double& im1) {
-    const int e0 = a.first[0] + a.n_used, e1 = a.first[1] + a.n_used;
-    for (int p = p0; p < p1; ++p) {
-        const PairGeo g = a.geo[p];
-        const double dx = fma(vfx, g.dt, gx0) - g.px;
-        const double dy = fma(vfy, g.dt, gy0) - g.py;
-        const double dz = vfz * g.dt - g.pz;
-        const double s_tx = fma(dx, dx, fma(dy, dy, dz * dz));
-        const double inv_d = rsqrt(s_tx);                                                   // one reciprocal square root
-        const double d_tx = s_tx * inv_d;                                                   // for both channels
-        const double dv = g.ux * dx + g.uy * dy + g.uz * dz;
-        if (p >= a.first[0] && p < e0) tdbp_pair_pixel<SERIES>(a, a.ch[0], s_tx, inv_d, d_tx, dv, a.off[0], p, re0, im0);
-        if (p >= a.first[1] && p < e1) tdbp_pair_pixel<SERIES>(a, a.ch[1], s_tx, inv_d, d_tx, dv, a.off[1], p, re1, im1);
-    }
-}
-
-// The pair with the geometry expanded about the tile's reference pixel, as tdbp_tile_prologue / tdbp_tile_pixel do it: per
-// (tile, pulse) one lane computes, with D the vector from the transmitter to the reference pixel and q the pixel's offset from it,
-//   d_tx = d0 sqrt(1 + u),  u = (2 D.q + |q|^2) / d0^2            as d0 (1 + u/2 - u^2/8 + u^3/16), the series of tdbp_tile_pixel
-//   d_tx - d_rx(c) = E_c0 + grad E_c . q                          E_c0 = off (2 D.v^ - off) / (d0 + d_rx0) (no cancellation),
-//                                                                 grad E_c = u^_tx - u^_rx = (off d0 v^ - E_c0 D) / (d0 d_rx0)
-// The remainder of the second line is q^T (H(d) - H(d - off v^)) q / 2 with H the Hessian of the Euclidean norm; the third
-// derivative of the norm at x applied to (h, h, k), unit h and k, is (-(1 - a^2) b - 2 a h_perp . k_perp) / |x|^2 with a = h . x^,
-// b = k . x^, whose modulus is at most sqrt((1 - a^2)(1 + 3 a^2)) <= 2 / sqrt(3).  So |remainder| <= |q|^2 |off| / (sqrt(3) d^2),
-// d the nearest range less |off|; the launcher takes this form only when that and the d_tx series' omitted term both stay below
-// 1e-9 m over all pulses and both channels (tdbp_tile_ok, pair_tile_ok), otherwise the exact form above.
-struct __attribute__((aligned(16))) PairTilePulse {
-    double a1, a2;           // 2 Dx, 2 Dy
-    double inv_d0sq, d0;
-    double e0[2], ex[2], ey[2];
-};
-static_assert(sizeof(PairTilePulse) == 80, "five 16-byte LDS reads per pulse");
-
-// d: from the transmitter to the reference pixel moved with the focus velocity; u: v^ of this pulse
-__device__ __forceinline__ PairTilePulse tdbp_pair_tile_prologue(double dx, double dy, double dz, double ux, double uy, double uz, double off0,
-                                                                double off1) {
-    const double s0 = fma(dx, dx, fma(dy, dy, dz * dz));
-    const double inv_d = rsqrt(s0), d0 = s0 * inv_d;
-    const double dv = ux * dx + uy * dy + uz * dz;
-    PairTilePulse t;
-    t.a1 = 2.0 * dx; t.a2 = 2.0 * dy; t.inv_d0sq = inv_d * inv_d; t.d0 = d0;
-    const double off[2] = {off0, off1};
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const double d_rx = sqrt(fma(off[c], off[c] - 2.0 * dv, s0));
-        const double e0 = off[c] * (2.0 * dv - off[c]) / (d0 + d_rx);
-        const double inv = 1.0 / (d0 * d_rx);
-        t.e0[c] = e0;
-        t.ex[c] = (off[c] * d0 * ux - e0 * dx) * inv;
-        t.ey[c] = (off[c] * d0 * uy - e0 * dy) * inv;
-    }
-    return t;
-}
-
-// d_tx of one pixel and pulse, for every channel.  T: PairTilePulse, or MultiTilePulse<N> below (the same fields, N channels)
-template <class T> __device__ __forceinline__ double tdbp_pair_tile_dtx(const T& t, double qx, double qy, double q2) {
-    const double u = fma(t.a1, qx, fma(t.a2, qy, q2)) * t.inv_d0sq;
-    const double h = u * fma(u, fma(u, 1.0 / 16.0, -1.0 / 8.0), 0.5);
-    return fma(t.d0, h, t.d0);
-}
-
-template <class A, class T> __device__ __forceinline__ void tdbp_pair_tile_pixel(const A& c, const PairChan& ch, const T& t, int chan,
-                                                                      double d_tx, double qx, double qy, double two_inv_ns, int p,
-                                                                      double& acc_re, double& acc_im) {
-    const double e = fma(t.ex[chan], qx, fma(t.ey[chan], qy, t.e0[chan]));                  // d_tx - d_rx
-    const double tau = fma(2.0, d_tx, -e) * c.inv_c;
-    const double idx_f = (tau - c.t_start + c.chirp_centre) * c.fs;
-    const float xn = (float)fma(idx_f, two_inv_ns, -1.0);
-    tdbp_sample(ch, xn, tau, p, acc_re, acc_im);
-}
-
-// The pulses [p0, p1) in the tile form: one lane per pulse fills the batch's records s_tp [TP_BATCH] in LDS, then every pixel walks
-// them.  Every thread of the workgroup comes here, dead lanes too: the loop holds two barriers per batch.
-template <class A> __device__ __forceinline__ void tdbp_pair_tile_pulses(const A& a, PairTilePulse* s_tp, double vfx, double vfy, double vfz, const TdbpTileOffsets& o,
-                                                                       int p0, int p1, double& re0, double& im0, double& re1, double& im1) {
-    const int e0 = a.first[0] + a.n_used, e1 = a.first[1] + a.n_used;
-    const double two_inv_ns = 2.0 * a.inv_ns;
-    for (int pb = p0; pb < p1; pb += TP_BATCH) {
-        const int nb = min(TP_BATCH, p1 - pb);
-        __syncthreads();                                   // the previous batch has been consumed
-        if ((int)threadIdx.x < nb) {
-            const PairGeo g = a.geo[pb + threadIdx.x];
-            const double dx = fma(vfx, g.dt, o.xc) - g.px, dy = fma(vfy, g.dt, o.yc) - g.py, dz = vfz * g.dt - g.pz;
-            s_tp[threadIdx.x] = tdbp_pair_tile_prologue(dx, dy, dz, g.ux, g.uy, g.uz, a.off[0], a.off[1]);
-        }
-        __syncthreads();
-        for (int k = 0; k < nb; ++k) {
-            const int p = pb + k;
-            const double d_tx = tdbp_pair_tile_dtx(s_tp[k], o.qx, o.qy, o.q2);
-            if (p >= a.first[0] && p < e0) tdbp_pair_tile_pixel(a, a.ch[0], s_tp[k], 0, d_tx, o.qx, o.qy, two_inv_ns, p, re0, im0);
-            if (p >= a.first[1] && p < e1) tdbp_pair_tile_pixel(a, a.ch[1], s_tp[k], 1, d_tx, o.qx, o.qy, two_inv_ns, p, re1, im1);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// N = 2, 3 or 4 receivers (tdbp_multi.hip): the pair's geometry per channel, the transmit leg still computed once
-// per pixel and pulse.  Every channel's statements are the pair's own - the exact form calls tdbp_pair_pixel itself, the tile form
-// tdbp_pair_tile_dtx and tdbp_pair_tile_pixel on a record with N channels, and only the record's prologue is restated (operand for
-// operand, over N offsets) - so N = 2 gives the pair's bits.  A: MultiArgs; read here beside what tdbp_pair_pixel reads: geo, rc[N],
-// fc, half_w, n_s (one waveform for every channel: a PairChan is made of them per channel, so the arguments hold them once), off[N],
-// first[N], n_used.
-// ------------------------------------------------------------------------------------------------------------
+// The pulses [p0, p1) of one pixel at (gx0, gy0) under the focus velocity vf, every channel.  A channel accumulates only inside its
+// own pulse range (a wave-uniform test).
 template <int N, bool SERIES, class A> __device__ __forceinline__ void tdbp_multi_pulses(const A& a, double vfx, double vfy, double vfz, double gx0,
                                                                                         double gy0, int p0, int p1, double (&re)[N], double (&im)[N]) {
     for (int p = p0; p < p1; ++p) {
@@ -310,6 +222,17 @@ template <int N, bool SERIES, class A> __device__ __forceinline__ void tdbp_mult
             }
     }
 }
+
+// The same with the geometry expanded about the tile's reference pixel, as tdbp_tile_prologue / tdbp_tile_pixel do it: per
+// (tile, pulse) one lane computes, with D the vector from the transmitter to the reference pixel and q the pixel's offset from it,
+//   d_tx = d0 sqrt(1 + u),  u = (2 D.q + |q|^2) / d0^2            as d0 (1 + u/2 - u^2/8 + u^3/16), the series of tdbp_tile_pixel
+//   d_tx - d_rx(c) = E_c0 + grad E_c . q                          E_c0 = off (2 D.v^ - off) / (d0 + d_rx0) (no cancellation),
+//                                                                 grad E_c = u^_tx - u^_rx = (off d0 v^ - E_c0 D) / (d0 d_rx0)
+// The remainder of the second line is q^T (H(d) - H(d - off v^)) q / 2 with H the Hessian of the Euclidean norm; the third
+// derivative of the norm at x applied to (h, h, k), unit h and k, is (-(1 - a^2) b - 2 a h_perp . k_perp) / |x|^2 with a = h . x^,
+// b = k . x^, whose modulus is at most sqrt((1 - a^2)(1 + 3 a^2)) <= 2 / sqrt(3).  So |remainder| <= |q|^2 |off| / (sqrt(3) d^2),
+// d the nearest range less |off|; the launcher takes this form only when that and the d_tx series' omitted term both stay below
+// 1e-9 m over all pulses and every channel (tdbp_tile_ok, tdbp_pair_bounds), otherwise the exact form above.
 
 // the tile form's record: 32 + 24 N bytes, padded to a multiple of 16 (80, 112, 128)
 template <int N> struct __attribute__((aligned(16))) MultiTilePulse {
@@ -338,7 +261,25 @@ template <int N> __device__ __forceinline__ MultiTilePulse<N> tdbp_multi_tile_pr
     return t;
 }
 
-// every thread of the workgroup comes here, dead lanes too: two barriers per batch, as in tdbp_pair_tile_pulses
+// d_tx of one pixel and pulse, for every channel.  T: MultiTilePulse<N>
+template <class T> __device__ __forceinline__ double tdbp_pair_tile_dtx(const T& t, double qx, double qy, double q2) {
+    const double u = fma(t.a1, qx, fma(t.a2, qy, q2)) * t.inv_d0sq;
+    const double h = u * fma(u, fma(u, 1.0 / 16.0, -1.0 / 8.0), 0.5);
+    return fma(t.d0, h, t.d0);
+}
+
+template <class A, class T> __device__ __forceinline__ void tdbp_pair_tile_pixel(const A& c, const PairChan& ch, const T& t, int chan,
+                                                                      double d_tx, double qx, double qy, double two_inv_ns, int p,
+                                                                      double& acc_re, double& acc_im) {
+    const double e = fma(t.ex[chan], qx, fma(t.ey[chan], qy, t.e0[chan]));                  // d_tx - d_rx
+    const double tau = fma(2.0, d_tx, -e) * c.inv_c;
+    const double idx_f = (tau - c.t_start + c.chirp_centre) * c.fs;
+    const float xn = (float)fma(idx_f, two_inv_ns, -1.0);
+    tdbp_sample(ch, xn, tau, p, acc_re, acc_im);
+}
+
+// The pulses [p0, p1) in the tile form: one lane per pulse fills the batch's records s_tp [TP_BATCH] in LDS, then every pixel walks
+// them.  Every thread of the workgroup comes here, dead lanes too: the loop holds two barriers per batch.
 template <int N, class A> __device__ __forceinline__ void tdbp_multi_tile_pulses(const A& a, MultiTilePulse<N>* s_tp, double vfx, double vfy, double vfz,
                                                                                const TdbpTileOffsets& o, int p0, int p1, double (&re)[N], double (&im)[N]) {
     const double two_inv_ns = 2.0 * a.inv_ns;

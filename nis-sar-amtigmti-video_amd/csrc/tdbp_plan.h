@@ -1,7 +1,9 @@
-// The back-projection plan itself: what tdbp.hip, the focus-velocity search (tdbp_search.hip), the two-receiver pair (tdbp_pair.hip),
-// the search on the pair per GMTI report (tdbp_pair_search.hip) and the N-receiver stack (tdbp_multi.hip) share and no other unit sees: the plan, the geometry bounds, the scratch a
-// unit holds (TdbpScratch; TdbpHypScratch with a hypothesis table) and the kernel arguments they have in common (tdbp_fill_args, tdbp_pair_fill_args).
+// The back-projection plan itself: what tdbp.hip, the focus-velocity search (tdbp_search.hip), the N-receiver stack (tdbp_multi.hip), its
+// two-receiver case (tdbp_pair.hip) and the search on the pair per GMTI report (tdbp_pair_search.hip) share and no other unit sees: the
+// plan, the geometry bounds, the scratch a unit holds (TdbpScratch; TdbpHypScratch with a hypothesis table; TdbpRx with the channels of
+// a receiver stack) and the kernel arguments they have in common (tdbp_fill_args, tdbp_rx_fill_args).
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <vector>
@@ -42,9 +44,9 @@ struct Tdbp {
     double2 *part = nullptr, *img = nullptr;
     uint64_t bytes = 0;
     TdbpSearch* search = nullptr; // scratch of the focus-velocity search (tdbp_search.hip), made by its first call, freed by tdbp_destroy
-    TdbpPair* pair = nullptr;     // scratch of the two-receiver pair (tdbp_pair.hip), likewise
+    TdbpRx* pair = nullptr;       // scratch of the two-receiver pair, capacity 2 (tdbp_pair.hip), likewise
     TdbpPairSearch* pair_search = nullptr;   // scratch of the search on the pair (tdbp_pair_search.hip), likewise
-    TdbpMulti* multi = nullptr;   // scratch of the N-receiver stack (tdbp_multi.hip), likewise
+    TdbpRx* multi = nullptr;      // scratch of the N-receiver stack, capacity MAX_RX (tdbp_multi.hip), likewise
 };
 
 #define TCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
@@ -59,16 +61,16 @@ void tdbp_set_focus(std::vector<PulseGeo>& geo, const double* vel, const double*
 void tdbp_sample_window(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double t_start, double scene_size,
                         int* lo, int* hi);
 bool tdbp_tile_ok(const Tdbp* t, const std::vector<PulseGeo>& geo, const double* vf, double scene_size);
-// what those two bounds and the pair's own (pair_bounds) are made of: the transmit range of one pulse over the moved pixel rectangle of half
+// what those two bounds and the receivers' own (tdbp_pair_bounds) are made of: the transmit range of one pulse over the moved pixel rectangle of half
 // side h, sample indices to a window inside [0, n_s] (NaN-safe), the farthest pixel of a tile from its reference pixel (< 0: grid too thin)
 void moved_rect_range(const PulseGeo& g, const double* vf, double h, double* dmin, double* dmax);
 void tdbp_clamp_window(double imin, double imax, int n_s, int* lo, int* hi);
 double tdbp_tile_reach(const Tdbp* t, double scene_size);
-// the pair's own bounds over the pulses [u0, u1) for one focus velocity (tdbp_pair.hip): the sample window either channel can touch,
-// whether the series of tdbp_pair_pixel holds, and whether the pair's part of the tile expansion does
+// the receivers' own bounds over the pulses [u0, u1) for one focus velocity (tdbp_pair.hip), off_max the largest |offset|: the sample
+// window any channel can touch, whether the series of tdbp_pair_pixel holds, and whether the receivers' part of the tile expansion does
 void tdbp_pair_bounds(const Tdbp* t, const std::vector<PulseGeo>& geo, int u0, int u1, const double* vf, double t_start, double scene_size,
-                      const sarx_tdbp_pair_params* prm, int* lo, int* hi, bool* series, bool* tile);
-// the pair's table from the pulse table and the transmitter's velocity rows (none zero)
+                      double off_max, double chirp_centre, int* lo, int* hi, bool* series, bool* tile);
+// the receivers' table from the pulse table and the transmitter's velocity rows (none zero)
 void tdbp_pair_table(PairGeo* h_geo, const std::vector<PulseGeo>& geo, const double* vel, int n_p);
 // the pair scratch's buffer of channel 1's range-compressed pulses [n_p][n_s] (made with the scratch by the first call)
 hipError_t tdbp_pair_rc1(Tdbp* t, cf** rc1);
@@ -115,21 +117,46 @@ template <class A> void tdbp_fill_args(const Tdbp* t, double t_start, int per_ch
     a.inv_ns = 1.0 / (double)t->n_s; a.half_w = (float)t->n_s / 2.0f;
     a.n_p = t->n_p; a.n_s = t->n_s; a.nx = t->nx; a.ny = t->ny; a.per_chunk = per_chunk;
 }
-// the union [u0, u1) of the two channels' pulse ranges: what the pair's kernels loop over
-inline void tdbp_pair_union(const sarx_tdbp_pair_params* prm, int* u0, int* u1) {
-    *u0 = prm->first_pulse[0] < prm->first_pulse[1] ? prm->first_pulse[0] : prm->first_pulse[1];
-    *u1 = (prm->first_pulse[0] > prm->first_pulse[1] ? prm->first_pulse[0] : prm->first_pulse[1]) + prm->n_used;
-}
-// the kernel arguments that the pair's launch (PairArgs) and its search's launches (PairSearchArgs) share; s: whose table holds PairGeo
-template <class A> void tdbp_pair_fill_args(const Tdbp* t, const TdbpScratch* s, const cf* rc1, double t_start, const sarx_tdbp_pair_params* prm, A& a) {
-    a.ch[0].rc = t->rc; a.ch[1].rc = rc1;
-    for (int c = 0; c < 2; ++c) {
-        a.ch[c].fc = t->k.fc; a.ch[c].half_w = (float)t->n_s / 2.0f; a.ch[c].n_s = t->n_s;
+// What a receiver stack holds beside the plan (tdbp_multi.hip): the PairGeo table, the range-compressed pulses of channels 1 and up
+// (channel 0's are the plan's) with the raw staging of the host entry point, each made when first used, and both output forms.  The
+// plan keeps two: t->pair of capacity 2, which the pair's calls run on and whose channel 1 serves the pair's search, and t->multi of
+// capacity MAX_RX for the stack's calls - so each answers for its own calls only and a pair-only plan holds two channels' memory.
+struct TdbpRx : TdbpScratch {
+    int cap = 0;                                           // channels, fixed when made
+    cf* rc[MAX_RX - 1] = {};                               // [n_p][n_s] range-compressed pulses of channels 1 .. cap - 1
+    float2* raw[MAX_RX - 1] = {};                          // staging of the host entry point, likewise
+    double2* img128 = nullptr;                             // [cap][ny*nx]
+    float2* img64 = nullptr;
+};
+// inst: t->pair or t->multi, made here with cap channels when NULL; then the compressed buffers of n_rx <= cap channels
+hipError_t tdbp_rx_scratch(Tdbp* t, TdbpRx*& inst, int cap, int n_rx, TdbpRx** out);
+void tdbp_rx_free(TdbpRx* s);
+// device staging of a host entry point: the raw pulses of channels 1 .. n_rx - 1 [n_p][n_s] and both output forms [cap][ny][nx]
+hipError_t tdbp_rx_staging(Tdbp* t, TdbpRx*& inst, int cap, int n_rx, float2** d_raw, double2** d_img128, float2** d_img64);
+// bytes s holds on the device and a sum over its buffers' addresses (0, 0 for NULL)
+void tdbp_rx_held(const Tdbp* t, const TdbpRx* s, uint64_t* bytes, uint64_t* id);
+// the back-projection of prm->n_rx <= cap channels on inst; the arguments of tdbp_multi (tdbp_multi.h)
+hipError_t tdbp_rx(Tdbp* t, TdbpRx*& inst, int cap, const float2* const* raw, const double* pos, const double* vel, const double* t_pulses,
+                   double t_start, const double* vel_focus, double scene_size, const sarx_tdbp_multi_params* prm, int chunks,
+                   double2* d_img128, float2* d_img64, hipStream_t st);
+// What the parameters and the plan say of the arguments the receivers' loops read (RxArgs, tdbp_pixel.hpp), the union [u0, u1) of the
+// channels' pulse ranges among them; where the pulses and the table lie (rc, geo) the caller sets from the scratch it holds.
+inline void tdbp_rx_fill_args(const Tdbp* t, double t_start, const sarx_tdbp_multi_params* prm, RxArgs& a) {
+    a.u0 = a.u1 = prm->first_pulse[0];
+    for (int c = 0; c < prm->n_rx; ++c) {
         a.off[c] = prm->rx_offset_m[c]; a.first[c] = prm->first_pulse[c];
+        if (a.first[c] < a.u0) a.u0 = a.first[c];
+        if (a.first[c] > a.u1) a.u1 = a.first[c];
     }
+    a.u1 += prm->n_used;
     a.n_used = prm->n_used;
-    tdbp_pair_union(prm, &a.u0, &a.u1);
-    a.geo = (const PairGeo*)s->geo; a.xax = t->xax; a.yax = t->yax;
+    a.fc = t->k.fc; a.half_w = (float)t->n_s / 2.0f; a.n_s = t->n_s;
     a.inv_c = 1.0 / t->k.c; a.fs = t->k.fs; a.t_start = t_start; a.chirp_centre = prm->chirp_centre_s; a.inv_ns = 1.0 / (double)t->n_s;
+}
+// the largest |offset| of the channels: all that tdbp_pair_bounds reads of them
+inline double tdbp_rx_off_max(const RxArgs& a, int n_rx) {
+    double om = 0.0;
+    for (int c = 0; c < n_rx; ++c) om = fmax(om, fabs(a.off[c]));
+    return om;
 }
 }  // namespace sarx
