@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _tdbp_host as _host
 from ._ffi import check
 from .echo import synth_device
 from .engine import DeviceBuffer, default_context
@@ -135,26 +135,18 @@ class TdbpPlan:
 
     def focus(self, raw, pos_plat, vel_plat, t_start, vel_focus, t_pulses, scene_size, want_rc=False, d_image=None):
         n_p, n_s, nx, ny = self.shape
-        pos = np.ascontiguousarray(pos_plat, dtype=np.float64)
-        vel = np.ascontiguousarray(vel_plat, dtype=np.float64)
-        tp = np.ascontiguousarray(t_pulses, dtype=np.float64)
-        vf = np.ascontiguousarray(vel_focus, dtype=np.float64)
-        if pos.shape != (n_p, 3) or vel.shape != (n_p, 3) or tp.shape != (n_p,) or vf.shape != (3,):
-            raise ValueError("pos_plat/vel_plat must be [n_pulses x 3], t_pulses [n_pulses], vel_focus [3]")
-        img = np.empty((ny, nx), dtype=np.complex128)
+        pos, vel, tp, vf = _host.geometry(n_p, pos_plat, vel_plat, t_pulses, vel_focus)
         lib, ctx = self.ctx.lib, self.ctx
-        if isinstance(raw, DeviceBuffer) and d_image is not None:      # device in, device out: only enqueues, returns nothing
+        if isinstance(raw, DeviceBuffer):       # into d_image: only enqueues, returns nothing; else into the kept image, downloaded
+            if d_image is None and self._d_img is None:
+                self._d_img = ctx.alloc(ny * nx * 16)
+            d_out = self._d_img if d_image is None else d_image
             check(lib.sarx_tdbp_focus_dev(self.h, raw.ptr, pos.ctypes.data, vel.ctypes.data, tp.ctypes.data, float(t_start),
-                                          vf.ctypes.data, float(scene_size), d_image.ptr), ctx.h)
-            return None
+                                          vf.ctypes.data, float(scene_size), d_out.ptr), ctx.h)
+            return None if d_image is not None else d_out.download(np.complex128, (ny, nx))
         if d_image is not None:
             raise ValueError("d_image needs a device input")
-        if isinstance(raw, DeviceBuffer):
-            if self._d_img is None:
-                self._d_img = ctx.alloc(img.nbytes)
-            check(lib.sarx_tdbp_focus_dev(self.h, raw.ptr, pos.ctypes.data, vel.ctypes.data, tp.ctypes.data, float(t_start),
-                                          vf.ctypes.data, float(scene_size), self._d_img.ptr), ctx.h)
-            return self._d_img.download(np.complex128, (ny, nx))
+        img = np.empty((ny, nx), dtype=np.complex128)
         x = np.ascontiguousarray(raw, dtype=np.complex64)
         if x.shape != (n_p, n_s):
             raise ValueError(f"raw must be [{n_p} x {n_s}]")

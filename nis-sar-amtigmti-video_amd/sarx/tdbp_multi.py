@@ -12,11 +12,11 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi, slot as _slot
+from . import _ffi, _tdbp_host as _host, slot as _slot
 from ._ffi import check
 from .engine import DeviceArray, default_context
 from .tdbp import batch_constants, cached_plan
-from .tdbp_pair import TdbpPairResult, _raw_ptr
+from .tdbp_pair import TdbpPairResult
 
 RECORD_DTYPE = np.dtype([("v_los", "<f8"), ("v_coarse", "<f8"), ("cost", "<f8"), ("cost_next", "<f8"), ("phase", "<f8", (3,)),
                          ("k", "<i4"), ("status", "<u4")])
@@ -32,8 +32,7 @@ def aligned_pulse_ranges(rx_offsets, vel_tx, t_pulses):
     if len(tp) < 2:
         raise ValueError("aligned pulse ranges need at least two pulses")
     prf = (len(tp) - 1) / float(tp[-1] - tp[0])
-    speed = float(np.mean(np.linalg.norm(np.asarray(vel_tx, dtype=np.float64), axis=1)))
-    m = (off - off[0]) * prf / (2.0 * speed)
+    m = (off - off[0]) * prf / (2.0 * _host.mean_speed(vel_tx))
     mi = np.rint(m)
     if np.any(np.abs(m - mi) > 1e-6):
         raise ValueError(f"the phase centres lie {m.tolist()} pulses apart, not whole pulses: pass pulse_ranges=((first_c ...), n_used)")
@@ -93,28 +92,18 @@ class TdbpMultiResult:
         md, stack, on_device = _slot.stage(reports, max_detections=max_detections, single=True)
         prm = resolve_params(self.lags_s, self.wavelength, v_max, half, md)
         check(ctx.lib.sarx_tdbp_multi_resolve_check(C.byref(prm)))
-        held = []
-        try:
+        with _host.temporaries() as held:
             if isinstance(self.imgs, np.ndarray):
                 ny, nx = self.imgs.shape[1:]
-                held.append(ctx.to_device(np.ascontiguousarray(self.imgs, dtype=np.complex64)))
-                p_img = held[-1].ptr
+                p_img = _host.hold(held, ctx.to_device(np.ascontiguousarray(self.imgs, dtype=np.complex64))).ptr
             else:
                 ny, nx = self.imgs[0].shape
                 p_img = self.imgs[0].ptr
-            if on_device:
-                p_slot = on_device[0][1]
-            else:
-                held.append(ctx.to_device(stack[0]))
-                p_slot = held[-1].ptr
-            rec = ctx.alloc(md * RECORD_DTYPE.itemsize)
-            held.append(rec)
+            p_slot = _host.slot_on_device(ctx, stack, on_device, held)
+            rec = _host.hold(held, ctx.alloc(md * RECORD_DTYPE.itemsize))
             check(ctx.lib.sarx_tdbp_multi_resolve_dev(ctx.h, C.byref(prm), p_img, int(ny), int(nx), p_slot, rec.ptr), ctx.h)
             count = _slot.raise_if_overflowed(*_slot.header(_slot.fetch_header(ctx, p_slot)), md, strict=True)
             return _slot.download(ctx, rec.ptr, count * RECORD_DTYPE.itemsize).view(RECORD_DTYPE).copy()
-        finally:
-            for b in held:
-                b.release()
 
     def release(self):
         """Frees a device-resident stack."""
@@ -136,56 +125,15 @@ def tdbp_multi(raws, pos_tx, vel_tx, rx_offsets, t_start, num_samples, t_pulses,
     Returns a TdbpMultiResult."""
     k = consts or batch_constants()
     ctx = ctx or default_context()
-    n_p, n_s, nx, ny = len(t_pulses), int(num_samples), int(nx), int(ny)
-    dtype = np.dtype(dtype or (np.complex64 if device_output else np.complex128))
-    if dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)) or (device_output and dtype != np.dtype(np.complex64)):
-        raise ValueError("dtype must be complex128 or complex64 (complex64 with device_output)")
-    pos = np.ascontiguousarray(pos_tx, dtype=np.float64)
-    vel = np.ascontiguousarray(vel_tx, dtype=np.float64)
-    tp = np.ascontiguousarray(t_pulses, dtype=np.float64)
-    vf = np.ascontiguousarray(vel_focus, dtype=np.float64)
-    if pos.shape != (n_p, 3) or vel.shape != (n_p, 3) or tp.shape != (n_p,) or vf.shape != (3,):
-        raise ValueError("pos_tx/vel_tx must be [n_pulses x 3], t_pulses [n_pulses], vel_focus [3]")
-    off = np.asarray(rx_offsets, dtype=np.float64)
-    n_rx = len(off)
-    if len(raws) != n_rx:
-        raise ValueError("one raw array per receiver offset")
-    if pulse_ranges is None:
-        pulse_ranges = aligned_pulse_ranges(off, vel, tp)
-    prm = multi_params(n_p, off, k["T_P"] / 2 if chirp_centre is None else chirp_centre, pulse_ranges)
-    check(ctx.lib.sarx_tdbp_multi_check(n_p, C.byref(prm)))
-    plan = cached_plan(ctx, k, n_p, n_s, nx, ny)
-    keep = []
-    ptrs, devs = zip(*(_raw_ptr(r, n_p, n_s, keep) for r in raws))
-    if len(set(devs)) != 1:
-        raise ValueError("the raw arrays must all be host arrays or all device-resident")
-    if device_output and not devs[0]:
-        raise ValueError("device_output needs device-resident raw")
-    wide = dtype == np.dtype(np.complex128)
-    p_raw = (C.c_void_p * n_rx)(*ptrs)
-    args = (p_raw, pos.ctypes.data, vel.ctypes.data, tp.ctypes.data, float(t_start), vf.ctypes.data, float(scene_size), C.byref(prm))
-    lib = ctx.lib
-    check(lib.sarx_tdbp_search_set_chunks(plan.h, 0 if chunks is None else int(chunks)), ctx.h)      # the plan's chunk count serves this too
+    lib, ny, nx = ctx.lib, int(ny), int(nx)
+    stack, lags, route = _host.focus_channels(
+        lib.sarx_tdbp_multi_check, lib.sarx_tdbp_multi_dev, lib.sarx_tdbp_multi_host, lib.sarx_tdbp_multi_route,
+        lambda n_p, off, vel, tp, centre: multi_params(n_p, off, centre,
+                                                       aligned_pulse_ranges(off, vel, tp) if pulse_ranges is None else pulse_ranges),
+        lambda ptrs: ((C.c_void_p * len(ptrs))(*ptrs),), cached_plan,
+        ctx, k, raws, pos_tx, vel_tx, rx_offsets, t_start, num_samples, t_pulses, scene_size, nx, ny, vel_focus, chirp_centre,
+        device_output, dtype, chunks)
     buf = None
-    if devs[0]:
-        buf = ctx.alloc(n_rx * ny * nx * dtype.itemsize)
-        try:
-            check(lib.sarx_tdbp_multi_dev(plan.h, *args, buf.ptr if wide else None, None if wide else buf.ptr), ctx.h)
-            if device_output:
-                imgs = [DeviceArray(buf, (ny, nx), offset=c * ny * nx * 8, owner=False) for c in range(n_rx)]
-            else:
-                imgs = buf.download(dtype, (n_rx, ny, nx))
-        except BaseException:
-            buf.release()
-            raise
-        if not device_output:
-            buf.release()
-            buf = None
-    else:
-        imgs = np.empty((n_rx, ny, nx), dtype=dtype)
-        check(lib.sarx_tdbp_multi_host(plan.h, *args, imgs.ctypes.data if wide else None, None if wide else imgs.ctypes.data), ctx.h)
-    tile = C.c_int()
-    check(lib.sarx_tdbp_multi_route(plan.h, C.byref(tile)), ctx.h)
-    speed = float(np.mean(np.linalg.norm(vel, axis=1)))
-    lags = (off[1:] - off[0]) / (2.0 * speed)
-    return TdbpMultiResult(imgs, lags, k["C"] / k["FC"], "tile" if tile.value else "exact", ctx, buf)
+    if device_output:                           # views of the one buffer, which the result owns
+        buf, stack = stack, [DeviceArray(stack, (ny, nx), offset=c * ny * nx * 8, owner=False) for c in range(len(raws))]
+    return TdbpMultiResult(stack, lags, k["C"] / k["FC"], route, ctx, buf)

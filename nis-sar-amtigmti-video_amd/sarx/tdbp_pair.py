@@ -16,9 +16,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi
-from ._ffi import check
-from .engine import DeviceArray, DeviceBuffer, default_context
+from . import _ffi, _tdbp_host as _host
+from .engine import DeviceArray, default_context
 from .tdbp import batch_constants, cached_plan
 
 
@@ -80,20 +79,6 @@ def pair_params(n_pulses, rx_offsets, chirp_centre, pulse_shift):
     return _ffi.TdbpPairParams((C.c_double * 2)(*off), float(chirp_centre), (C.c_int32 * 2)(int(first[0]), int(first[1])), int(n_used), 0)
 
 
-def _raw_ptr(x, n_p, n_s, keep):
-    if isinstance(x, (DeviceBuffer, DeviceArray)):
-        if isinstance(x, DeviceArray) and (x.shape != (n_p, n_s) or x.transposed):
-            raise ValueError(f"device raw must be [{n_p} x {n_s}] row-major")
-        if x.nbytes < n_p * n_s * 8:
-            raise ValueError("device raw smaller than [n_pulses x num_samples] complex64")
-        return x.ptr, True
-    a = np.ascontiguousarray(x, dtype=np.complex64)
-    if a.shape != (n_p, n_s):
-        raise ValueError(f"raw must be [{n_p} x {n_s}]")
-    keep.append(a)
-    return a.ctypes.data, False
-
-
 def tdbp_pair(raw1, raw2, pos_tx, vel_tx, rx_offsets, t_start, num_samples, t_pulses, scene_size, nx=512, ny=512, *,
               vel_focus=(0.0, 0.0, 0.0), chirp_centre=None, pulse_shift=True, consts=None, ctx=None, device_output=False, dtype=None,
               chunks=None):
@@ -111,49 +96,12 @@ def tdbp_pair(raw1, raw2, pos_tx, vel_tx, rx_offsets, t_start, num_samples, t_pu
     Returns a TdbpPairResult; its ``route`` tells whether the tile-expanded kernel ran or the exact one."""
     k = consts or batch_constants()
     ctx = ctx or default_context()
-    n_p, n_s, nx, ny = len(t_pulses), int(num_samples), int(nx), int(ny)
-    dtype = np.dtype(dtype or (np.complex64 if device_output else np.complex128))
-    if dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)) or (device_output and dtype != np.dtype(np.complex64)):
-        raise ValueError("dtype must be complex128 or complex64 (complex64 with device_output)")
-    pos = np.ascontiguousarray(pos_tx, dtype=np.float64)
-    vel = np.ascontiguousarray(vel_tx, dtype=np.float64)
-    tp = np.ascontiguousarray(t_pulses, dtype=np.float64)
-    vf = np.ascontiguousarray(vel_focus, dtype=np.float64)
-    if pos.shape != (n_p, 3) or vel.shape != (n_p, 3) or tp.shape != (n_p,) or vf.shape != (3,):
-        raise ValueError("pos_tx/vel_tx must be [n_pulses x 3], t_pulses [n_pulses], vel_focus [3]")
-    prm = pair_params(n_p, rx_offsets, k["T_P"] / 2 if chirp_centre is None else chirp_centre, pulse_shift)
-    check(ctx.lib.sarx_tdbp_pair_check(n_p, C.byref(prm)))
-    plan = cached_plan(ctx, k, n_p, n_s, nx, ny)
-    keep = []
-    p1, dev1 = _raw_ptr(raw1, n_p, n_s, keep)
-    p2, dev2 = _raw_ptr(raw2, n_p, n_s, keep)
-    if dev1 != dev2:
-        raise ValueError("raw1 and raw2 must both be host arrays or both device-resident")
-    if device_output and not dev1:
-        raise ValueError("device_output needs device-resident raw")
-    wide = dtype == np.dtype(np.complex128)
-    args = (pos.ctypes.data, vel.ctypes.data, tp.ctypes.data, float(t_start), vf.ctypes.data, float(scene_size), C.byref(prm))
-    lib = ctx.lib
-    check(lib.sarx_tdbp_search_set_chunks(plan.h, 0 if chunks is None else int(chunks)), ctx.h)      # the plan's chunk count serves both
-    if dev1:
-        buf = ctx.alloc(2 * ny * nx * dtype.itemsize)
-        try:
-            check(lib.sarx_tdbp_pair_dev(plan.h, p1, p2, *args, buf.ptr if wide else None, None if wide else buf.ptr), ctx.h)
-            if device_output:
-                imgs = (DeviceArray(buf, (ny, nx)), DeviceArray(buf, (ny, nx), offset=ny * nx * 8, owner=False))
-            else:
-                imgs = buf.download(dtype, (2, ny, nx))
-        finally:
-            if not device_output:
-                buf.release()
-    else:
-        imgs = np.empty((2, ny, nx), dtype=dtype)
-        check(lib.sarx_tdbp_pair_host(plan.h, p1, p2, *args, imgs.ctypes.data if wide else None, None if wide else imgs.ctypes.data), ctx.h)
-    tile = C.c_int()
-    check(lib.sarx_tdbp_pair_route(plan.h, C.byref(tile)), ctx.h)
-    off = np.asarray(rx_offsets, dtype=np.float64)
-    speed = float(np.mean(np.linalg.norm(vel, axis=1)))
-    # the phase centres (midway between transmitter and receiver) lie (off2 - off1) / 2 apart along track: the second one passes
-    # a point this much later (with offsets -+ V / PRF and the DPCA pulse shift: exactly one pulse interval)
-    lag = (off[1] - off[0]) / (2.0 * speed)
-    return TdbpPairResult(imgs[0], imgs[1], lag, k["C"] / k["FC"], "tile" if tile.value else "exact", ctx)
+    lib, ny, nx = ctx.lib, int(ny), int(nx)
+    stack, lags, route = _host.focus_channels(
+        lib.sarx_tdbp_pair_check, lib.sarx_tdbp_pair_dev, lib.sarx_tdbp_pair_host, lib.sarx_tdbp_pair_route,
+        lambda n_p, off, vel, tp, centre: pair_params(n_p, off, centre, pulse_shift), lambda ptrs: ptrs, cached_plan,
+        ctx, k, (raw1, raw2), pos_tx, vel_tx, rx_offsets, t_start, num_samples, t_pulses, scene_size, nx, ny, vel_focus, chirp_centre,
+        device_output, dtype, chunks)
+    if device_output:                           # two views of the one buffer; the first owns it
+        stack = (DeviceArray(stack, (ny, nx)), DeviceArray(stack, (ny, nx), offset=ny * nx * 8, owner=False))
+    return TdbpPairResult(stack[0], stack[1], lags[0], k["C"] / k["FC"], route, ctx)

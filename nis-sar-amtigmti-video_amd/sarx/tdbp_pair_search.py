@@ -12,12 +12,12 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi, slot as _slot
+from . import _ffi, _tdbp_host as _host, slot as _slot
 from ._ffi import check
 from .engine import default_context
 from .tdbp import batch_constants, cached_plan
-from .tdbp_pair import _raw_ptr, pair_params
-from .tdbp_search import RECORD_DTYPE, TdbpSearchResult, _check_hyps
+from .tdbp_pair import pair_params
+from .tdbp_search import RECORD_DTYPE, TdbpSearchResult
 
 BEST_DTYPE = np.dtype([("k_best", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("peak_ix", "<i4"), ("peak_iy", "<i4"), ("reserved", "<i4"),
                        ("s4_prev", "<f8"), ("s4_best", "<f8"), ("s4_next", "<f8"), ("interf_re", "<f8"), ("interf_im", "<f8"),
@@ -78,44 +78,24 @@ def tdbp_pair_search(raw1, raw2, pos_tx, vel_tx, rx_offsets, t_start, num_sample
     k = consts or batch_constants()
     ctx = ctx or default_context()
     n_p, n_s, nx, ny = len(t_pulses), int(num_samples), int(nx), int(ny)
-    hyp = _check_hyps(vel_hyps)
+    hyp = _host.hypotheses(vel_hyps)
     n_hyp = hyp.shape[0]
-    pos = np.ascontiguousarray(pos_tx, dtype=np.float64)
-    vel = np.ascontiguousarray(vel_tx, dtype=np.float64)
-    tp = np.ascontiguousarray(t_pulses, dtype=np.float64)
-    if pos.shape != (n_p, 3) or vel.shape != (n_p, 3) or tp.shape != (n_p,):
-        raise ValueError("pos_tx/vel_tx must be [n_pulses x 3], t_pulses [n_pulses]")
-    prm = pair_params(n_p, rx_offsets, k["T_P"] / 2 if chirp_centre is None else chirp_centre, pulse_shift)
+    pos, vel, tp, _ = _host.geometry(n_p, pos_tx, vel_tx, t_pulses)
+    prm = pair_params(n_p, rx_offsets, _host.chirp_centre(k, chirp_centre), pulse_shift)
     sp = search_params(chip, n_hyp, source)
     lib = ctx.lib
     check(lib.sarx_tdbp_pair_check(n_p, C.byref(prm)))
     check(lib.sarx_tdbp_pair_search_check(C.byref(sp), nx, ny))
     md, stack, on_device = _slot.stage(reports, detect, max_detections, single=True)
     plan = cached_plan(ctx, k, n_p, n_s, nx, ny)
-    keep, temps = [], []
-    try:
-        ptrs = []
-        for raw in (raw1, raw2):
-            p, dev = _raw_ptr(raw, n_p, n_s, keep)
-            if not dev:
-                temps.append(ctx.to_device(keep[-1]))
-                p = temps[-1].ptr
-            ptrs.append(p)
-        if on_device:
-            slot_ptr = on_device[0][1]
-        else:
-            temps.append(ctx.to_device(stack[0]))
-            slot_ptr = temps[-1].ptr
+    with _host.temporaries() as held:
+        p1, p2 = _host.raw_on_device(ctx, (raw1, raw2), n_p, n_s, held)
+        slot_ptr = _host.slot_on_device(ctx, stack, on_device, held)
         n_chip = sp.chip_x * sp.chip_y
-        d_rec = ctx.alloc(md * n_hyp * RECORD_DTYPE.itemsize)
-        temps.append(d_rec)
-        d_best = ctx.alloc(md * BEST_DTYPE.itemsize)
-        temps.append(d_best)
-        d_chips = None
-        if chips:
-            d_chips = ctx.alloc(md * n_hyp * 2 * n_chip * 16)
-            temps.append(d_chips)
-        check(lib.sarx_tdbp_pair_search_dev(plan.h, ptrs[0], ptrs[1], pos.ctypes.data, vel.ctypes.data, tp.ctypes.data, float(t_start),
+        d_rec = _host.hold(held, ctx.alloc(md * n_hyp * RECORD_DTYPE.itemsize))
+        d_best = _host.hold(held, ctx.alloc(md * BEST_DTYPE.itemsize))
+        d_chips = _host.hold(held, ctx.alloc(md * n_hyp * 2 * n_chip * 16)) if chips else None
+        check(lib.sarx_tdbp_pair_search_dev(plan.h, p1, p2, pos.ctypes.data, vel.ctypes.data, tp.ctypes.data, float(t_start),
                                             float(scene_size), C.byref(prm), hyp.ctypes.data, slot_ptr + _slot.HEADER_BYTES, slot_ptr, md,
                                             C.byref(sp), d_rec.ptr, d_best.ptr, d_chips.ptr if chips else None), ctx.h)
         count = _slot.raise_if_overflowed(*_slot.header(_slot.fetch_header(ctx, slot_ptr)), md, strict=True)
@@ -125,18 +105,11 @@ def tdbp_pair_search(raw1, raw2, pos_tx, vel_tx, rx_offsets, t_start, num_sample
         if chips:
             stack_c = _slot.download(ctx, d_chips.ptr, count * n_hyp * 2 * n_chip * 16).view(np.complex128).reshape(
                 count, n_hyp, 2, sp.chip_y, sp.chip_x).copy()
-    finally:
-        for b in temps:
-            b.release()
     out = best["k_best"] < 0                                        # outside the grid: the library wrote k_best alone
-    for f in BEST_DTYPE.names[1:]:
-        best[f][out] = -1 if BEST_DTYPE[f].kind == "i" else np.nan
-    for f in RECORD_DTYPE.names:
-        rec[f][out] = -1 if RECORD_DTYPE[f].kind == "i" else np.nan
+    for a, names in ((best, BEST_DTYPE.names[1:]), (rec, RECORD_DTYPE.names)):
+        for f in names:
+            a[f][out] = -1 if a.dtype[f].kind == "i" else np.nan
     if stack_c is not None:
         stack_c[out] = np.nan
-    tile = C.c_int()
-    check(lib.sarx_tdbp_pair_search_route(plan.h, C.byref(tile)), ctx.h)
-    off = np.asarray(rx_offsets, dtype=np.float64)
-    lag = (off[1] - off[0]) / (2.0 * float(np.mean(np.linalg.norm(vel, axis=1))))      # as tdbp_pair has it
-    return TdbpPairSearchResult(hyp.copy(), rec, best, stack_c, "tile" if tile.value else "exact", lag, k["C"] / k["FC"])
+    return TdbpPairSearchResult(hyp.copy(), rec, best, stack_c, _host.route(lib.sarx_tdbp_pair_search_route, plan),
+                                _host.lags(rx_offsets, vel)[0], k["C"] / k["FC"])

@@ -9,11 +9,9 @@ ALONG-TRACK component only (a ground-range mismatch displaces the target, it doe
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _tdbp_host as _host
 from ._ffi import check
 from .engine import DeviceBuffer, default_context
 from .tdbp import batch_constants, cached_plan, tdbp_gpu
@@ -104,13 +102,6 @@ class TdbpSearchResult:
         return TdbpEstimate(v[b] + frac * step_vec, s_b + frac * step, b, False, metric)
 
 
-def _check_hyps(vel_hyps):
-    hyp = np.ascontiguousarray(vel_hyps, dtype=np.float64)
-    if hyp.ndim != 2 or hyp.shape[1] != 3:
-        raise ValueError("vel_hyps must be [n_hyp x 3]")
-    return hyp
-
-
 def tdbp_search(raw_t, pos_plat, vel_plat, t_start, num_samples, vel_hyps, t_pulses, scene_size, nx, ny, *, images=False,
                 consts=None, ctx=None, chunks=None):
     """Back-projection of one CPI under every focus velocity of ``vel_hyps`` [n_hyp x 3] in one enqueue (arguments as
@@ -118,17 +109,13 @@ def tdbp_search(raw_t, pos_plat, vel_plat, t_start, num_samples, vel_hyps, t_pul
     ``images=True`` also returns the stack.  ``chunks``: pulse chunks (None = chosen by the library)."""
     k = consts or batch_constants()
     ctx = ctx or default_context()
-    hyp = _check_hyps(vel_hyps)
+    hyp = _host.hypotheses(vel_hyps)
     n_hyp, n_p = hyp.shape[0], len(t_pulses)
     plan = cached_plan(ctx, k, n_p, num_samples, nx, ny)
     nx, ny = int(nx), int(ny)
-    pos = np.ascontiguousarray(pos_plat, dtype=np.float64)
-    vel = np.ascontiguousarray(vel_plat, dtype=np.float64)
-    tp = np.ascontiguousarray(t_pulses, dtype=np.float64)
-    if pos.shape != (n_p, 3) or vel.shape != (n_p, 3) or tp.shape != (n_p,):
-        raise ValueError("pos_plat/vel_plat must be [n_pulses x 3], t_pulses [n_pulses]")
+    pos, vel, tp, _ = _host.geometry(n_p, pos_plat, vel_plat, t_pulses)
     lib = ctx.lib
-    check(lib.sarx_tdbp_search_set_chunks(plan.h, 0 if chunks is None else int(chunks)), ctx.h)
+    _host.set_chunks(plan, chunks)
     rec = np.zeros(max(n_hyp, 1), dtype=RECORD_DTYPE)
     stack = None
     if isinstance(raw_t, DeviceBuffer):
@@ -159,9 +146,7 @@ def tdbp_search(raw_t, pos_plat, vel_plat, t_start, num_samples, vel_hyps, t_pul
                                         hyp.ctypes.data, n_hyp, float(scene_size), stack.ctypes.data if stack is not None else None,
                                         rec.ctypes.data), ctx.h)
         rec = rec[:n_hyp]
-    tile = C.c_int()
-    check(lib.sarx_tdbp_search_route(plan.h, C.byref(tile)), ctx.h)
-    return TdbpSearchResult(hyp.copy(), rec, stack, "tile" if tile.value else "exact")
+    return TdbpSearchResult(hyp.copy(), rec, stack, _host.route(lib.sarx_tdbp_search_route, plan))
 
 
 def tdbp_autofocus(raw_t, pos_plat, vel_plat, t_start, num_samples, t_pulses, scene_size, nx, ny, *, v0, half_span, n,
