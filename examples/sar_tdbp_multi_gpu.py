@@ -8,9 +8,10 @@ to the middle of the chip.  The receivers ride at (-d, +d, -d + 10 d), d = V / P
 (unambiguous to +-38.8 m/s) and a long one of five (+-7.8 m/s).  All three are back-projected onto ONE ground chip in one enqueue;
 the short pair goes through sarx.gmti_detect, and every report is resolved on the device.  Prints, for the strongest report, the
 speed the long baseline gives alone (wrapped: near -3.5 m/s, the wrong sign), the short baseline's, and the resolved one (near
-12 m/s) against the geometry's.
+12 m/s) against the geometry's.  With --relocate the resolved speed puts the report back on the ground (sarx.ground_relocate, DESIGN.md
+4.21): the chip shows the mover near (0, 0) m, it is at (49.5 * speed, 0) m.
 
-    python3 examples/sar_tdbp_multi_gpu.py [--pulses 320] [--speed 16] [--nx 90] [--ny 70] [--scene-size 360]"""
+    python3 examples/sar_tdbp_multi_gpu.py [--pulses 320] [--speed 16] [--nx 90] [--ny 70] [--scene-size 360] [--relocate]"""
 import argparse
 import os
 import sys
@@ -27,6 +28,7 @@ def main():
     ap.add_argument("--nx", type=int, default=90)
     ap.add_argument("--ny", type=int, default=70)
     ap.add_argument("--scene-size", type=float, default=360.0)
+    ap.add_argument("--relocate", action="store_true", help="also relocate the reports to their ground position by the resolved speed")
     a = ap.parse_args()
     import sarx
     kb = sarx.batch_constants()
@@ -74,6 +76,16 @@ def main():
         print(f"resolved             : k = {best['k']}, v_los {best['v_los']:+.3f} m/s; cost {best['cost']:.2e}, the next wrap count's "
               f"{best['cost_next']:.3f}")
         print(f"geometry             : v_los {v_true:+.3f} m/s")
+        if a.relocate:
+            # the short pair's mean phase centre at the reference time; an output grid wide enough for the along-track displacement
+            p_ref, v_ref = sarx.reference_geometry(pos, vel, t_vec, offs[:2])
+            span = 2.0 * (abs(p_m[0]) + a.scene_size)
+            out = sarx.ground_relocate(rep, rec["v_los"], valid=rec["status"], pos_ref=p_ref, vel_ref=v_ref, grid=(a.scene_size, a.nx, a.ny),
+                                       out_grid=(-span / 2, -span / 2, 4.0, 4.0, int(span / 4) + 1, int(span / 4) + 1))
+            g = out.records[r]
+            print(f"relocated            : ({g['x']:.1f}, {g['y']:.1f}) m, moved by ({g['shift_x']:+.1f}, {g['shift_y']:+.1f}) m; status {g['status']}, "
+                  f"{len(out.reports)} of {len(out)} reports on the ground grid")
+            print(f"the mover is at      : ({p_m[0]:.1f}, {p_m[1]:.1f}) m")
     res.release()
     for r in raws:
         r.release()

@@ -46,8 +46,11 @@
  *
  * Plain C99.  Extends include/sarx.h and include/sarx_gmti.h (the context, the error codes, sarx_tdbp_plan, the slot layout).
  *
+ * The records feed sarx_relocate.h as they lie on the device (v_los at offset 0, status at offset 60, stride 64): each report is
+ * put back at its ground position, and the relocated list is a slot the tracker takes.
+ *
  * Left out: the focus-velocity search on N channels, coherence-weighted costs, a maximum-likelihood combination of the baselines
- * after unwrapping, feeding the resolved speed into the tracker or into relocation on the ground grid. */
+ * after unwrapping. */
 #ifndef SARX_TDBP_MULTI_H
 #define SARX_TDBP_MULTI_H
 

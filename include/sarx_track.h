@@ -45,8 +45,11 @@
  * A report inside the gate of a track that did not take it starts nothing: that suppresses duplicate tracks beside a real one,
  * at the price of a late birth for a close neighbour (it is born once the neighbour's gate no longer holds it).
  *
- * Left out: a Kalman covariance, multi-hypothesis or globally optimal assignment, tracking in relocated ground coordinates, and
- * feeding the track velocity back into the refocus grid. */
+ * Tracking in ground coordinates: sarx_relocate.h makes the slots of this tracker from a frame's reports and their radial
+ * speeds, on a ground grid of the caller's choosing; the pixels here are then that grid's.
+ *
+ * Left out: a Kalman covariance, multi-hypothesis or globally optimal assignment, and feeding the track velocity back into the
+ * refocus grid. */
 #ifndef SARX_TRACK_H
 #define SARX_TRACK_H
 

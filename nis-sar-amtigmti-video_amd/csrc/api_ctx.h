@@ -1,5 +1,5 @@
 // What the host units of the C ABI share (api_ctx.hip, api_csa.hip, api_focus.hip, api_comm.hip; the detection chain's api_gmti.hip,
-// api_oscfar.hip, api_cluster.hip, api_atigate.hip, api_track.hip, api_balance.hip, api_coherence.hip through api_gmti.h; the back-projection's
+// api_oscfar.hip, api_cluster.hip, api_atigate.hip, api_track.hip, api_balance.hip, api_coherence.hip, api_relocate.hip through api_gmti.h; the back-projection's
 // api_tdbp_search.hip, api_tdbp_pair.hip, api_tdbp_pair_search.hip through api_tdbp.h): the context behind sarx_ctx*, its per-lane scratch,
 // error reporting, the exception guard and the staged host copies.  Host only: no kernel file includes this header.
 #pragma once
@@ -79,8 +79,8 @@ struct sarx_ctx {
     int range_impl = 0;                // SARX_RANGE_IMPL: 0 auto, 1 = 16 pts/thread, 2 = 32 pts/thread split exchange, 3 = fused wave-private, 4 = sixteen-wave permuted-spectrum pair
     // device scratch that an entry point keeps between calls, one of each per lane (two frames in flight must not share it): the unordered
     // report list sarx_gmti_refine_dev sorts from, the S_k that sarx_refocus_dev's record launch reads when the caller passes no curves, the
-    // keep flags between sarx_atigate_step_dev's two launches
-    enum Scratch { GMTI_COPY, REFOCUS_CURVES, ATIGATE_KEEP, N_SCRATCH };
+    // keep flags between sarx_atigate_step_dev's two launches, the sort keys between sarx_relocate_dev's two
+    enum Scratch { GMTI_COPY, REFOCUS_CURVES, ATIGATE_KEEP, RELOCATE_KEYS, N_SCRATCH };
     sarx::LaneScratch scratch[N_SCRATCH][LANES];
     sarx::LaneScratch& lane_scratch(Scratch k) { return scratch[k][cur_lane]; }
     std::string err;

@@ -21,6 +21,7 @@ from .tdbp_search import TdbpSearchResult, tdbp_autofocus, tdbp_search, tdbp_vel
 from .tdbp_pair import TdbpPairResult, tdbp_pair
 from .tdbp_pair_search import TdbpPairSearchResult, tdbp_pair_search
 from .tdbp_multi import TdbpMultiResult, tdbp_multi
+from .relocate import RelocateResult, ground_relocate, reference_geometry, relocate_frames
 from .focus import (FocusFuture, ati_dpca, clear_plan_cache, dpca_pulse_shift, focus_ati_dpca, focus_stream, phase_balance,
                     sar_focus_csa, sar_focus_csa_async, two_channel_workspace)
 
@@ -34,4 +35,5 @@ __all__ = ["SarxError", "Context", "CsaPlan", "FocusLanes", "add_noise_rel_dev",
            "gmti_cluster", "ClusterParams", "GmtiPlots", "gmti_ati_gate", "AtiGateParams",
            "tdbp_search", "tdbp_velocity_line", "tdbp_autofocus", "TdbpSearchResult",
            "tdbp_pair", "TdbpPairResult", "tdbp_pair_search", "TdbpPairSearchResult",
-           "tdbp_multi", "TdbpMultiResult"]
+           "tdbp_multi", "TdbpMultiResult",
+           "ground_relocate", "reference_geometry", "relocate_frames", "RelocateResult"]

@@ -429,6 +429,29 @@ TDBP_MULTI_SIGNATURES = {
     "sarx_tdbp_multi_resolve_dev": (_i, [_vp, _P(TdbpMultiResolveParams), _vp, _i, _i, _vp, _vp]),
 }
 
+# include/sarx_relocate.h: the ground relocation of GMTI reports, a fourteenth table bound the same way
+RELOCATE_OK, RELOCATE_NO_SPEED, RELOCATE_NO_SOLUTION, RELOCATE_OFF_GRID, RELOCATE_OVERFLOW = 0, 1, 2, 3, 4      # SARX_RELOCATE_*
+RELOCATE_HAS_VELOCITY = 1
+
+
+class RelocateParams(C.Structure):
+    """sarx_relocate_params (128 bytes)"""
+    _fields_ = [("pos_ref", C.c_double * 3), ("vel_ref", C.c_double * 3), ("in_x0", C.c_double), ("in_y0", C.c_double), ("in_dx", C.c_double),
+                ("in_dy", C.c_double), ("out_x0", C.c_double), ("out_y0", C.c_double), ("out_dx", C.c_double), ("out_dy", C.c_double),
+                ("out_nx", C.c_int32), ("out_ny", C.c_int32), ("max_detections", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RelocateRecord(C.Structure):
+    """sarx_relocate_record (64 bytes)"""
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("shift_x", C.c_double), ("shift_y", C.c_double), ("vx", C.c_double), ("vy", C.c_double),
+                ("rank", C.c_int32), ("status", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+RELOCATE_SIGNATURES = {
+    "sarx_relocate_check": (_i, [_P(RelocateParams)]),
+    "sarx_relocate_dev": (_i, [_vp, _P(RelocateParams), _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -444,7 +467,8 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(GMTI_SIGNATURES.items()) + list(REFOCUS_SIGNATURES.items()) + \
             list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()) + \
             list(CLUSTER_SIGNATURES.items()) + list(ATIGATE_SIGNATURES.items()) + list(TDBP_SEARCH_SIGNATURES.items()) + \
-            list(TDBP_PAIR_SIGNATURES.items()) + list(TDBP_PAIR_SEARCH_SIGNATURES.items()) + list(TDBP_MULTI_SIGNATURES.items()):
+            list(TDBP_PAIR_SIGNATURES.items()) + list(TDBP_PAIR_SEARCH_SIGNATURES.items()) + list(TDBP_MULTI_SIGNATURES.items()) + \
+            list(RELOCATE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
