@@ -48,8 +48,9 @@
  * Tracking in ground coordinates: sarx_relocate.h makes the slots of this tracker from a frame's reports and their radial
  * speeds, on a ground grid of the caller's choosing; the pixels here are then that grid's.
  *
- * Left out: a Kalman covariance, multi-hypothesis or globally optimal assignment, and feeding the track velocity back into the
- * refocus grid. */
+ * Left out: a Kalman covariance (sarx_ktrack.h has one, for reports relocated to the ground: metres, a Mahalanobis gate, the radial
+ * speed as a measurement), multi-hypothesis or globally optimal assignment, and feeding the track velocity back into the refocus
+ * grid. */
 #ifndef SARX_TRACK_H
 #define SARX_TRACK_H
 

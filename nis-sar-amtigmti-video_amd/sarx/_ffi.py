@@ -452,6 +452,48 @@ RELOCATE_SIGNATURES = {
     "sarx_relocate_dev": (_i, [_vp, _P(RelocateParams), _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
 }
 
+# include/sarx_ktrack.h: the Kalman ground tracker, a fifteenth table bound the same way
+KTRACK_MAX_TRACKS, KTRACK_MAX_DETECTIONS = 16384, 16384                       # SARX_KTRACK_MAX_TRACKS, _MAX_DETECTIONS
+KTRACK_FREE, KTRACK_TENTATIVE, KTRACK_CONFIRMED = 0, 1, 2
+KTRACK_OK, KTRACK_ERR_SLOT_OVERFLOW, KTRACK_ERR_TABLE_OVERFLOW, KTRACK_ERR_TIME = 0, 1, 2, 3
+
+
+class KtrackParams(C.Structure):
+    """sarx_ktrack_params (80 bytes)"""
+    _fields_ = [("sigma_pos", C.c_double), ("sigma_v", C.c_double), ("sigma_v_tan", C.c_double), ("q", C.c_double), ("gate_d2", C.c_double),
+                ("gate_m", C.c_double), ("birth_ratio", C.c_double), ("confirm_hits", C.c_int32), ("confirm_window", C.c_int32),
+                ("max_misses", C.c_int32), ("max_tracks", C.c_int32), ("max_detections", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KtrackFrame(C.Structure):
+    """sarx_ktrack_frame (64 bytes)"""
+    _fields_ = [("t", C.c_double), ("pos_ref", C.c_double * 3), ("vel_ref", C.c_double * 3), ("frame_index", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KtrackHeader(C.Structure):
+    """sarx_ktrack_header: the first 64 bytes of a Kalman track table"""
+    _fields_ = [("n_live", C.c_uint32), ("n_confirmed", C.c_uint32), ("next_id", C.c_int32), ("frames_done", C.c_uint32),
+                ("births_total", C.c_uint32), ("drops_total", C.c_uint32), ("error", C.c_uint32), ("error_frame", C.c_int32),
+                ("max_tracks", C.c_uint32), ("reserved0", C.c_uint32), ("t_last", C.c_double), ("reserved", C.c_uint32 * 4)]
+
+
+class KtrackSlot(C.Structure):
+    """sarx_ktrack_slot (192 bytes)"""
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("vx", C.c_double), ("vy", C.c_double), ("p", C.c_double * 10), ("sum_re", C.c_double),
+                ("sum_im", C.c_double), ("sum_power", C.c_double), ("max_ratio", C.c_double), ("nis_last", C.c_double), ("nis_sum", C.c_double),
+                ("id", C.c_int32), ("status", C.c_uint32), ("hits", C.c_uint32), ("misses", C.c_uint32), ("age", C.c_uint32),
+                ("hist", C.c_uint32), ("last_frame", C.c_int32), ("last_report", C.c_int32)]
+
+
+KTRACK_SIGNATURES = {
+    "sarx_ktrack_check": (_i, [_P(KtrackParams)]),
+    "sarx_ktrack_table_bytes": (_i, [_P(KtrackParams), _P(_sz)]),
+    "sarx_ktrack_workspace_bytes": (_i, [_P(KtrackParams), _P(_sz)]),
+    "sarx_ktrack_init_dev": (_i, [_vp, _P(KtrackParams), _vp]),
+    "sarx_ktrack_step_dev": (_i, [_vp, _P(KtrackParams), _P(KtrackFrame), _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "sarx_ktrack_run_dev": (_i, [_vp, _P(KtrackParams), _P(KtrackFrame), _i, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -468,7 +510,7 @@ def load():
             list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()) + \
             list(CLUSTER_SIGNATURES.items()) + list(ATIGATE_SIGNATURES.items()) + list(TDBP_SEARCH_SIGNATURES.items()) + \
             list(TDBP_PAIR_SIGNATURES.items()) + list(TDBP_PAIR_SEARCH_SIGNATURES.items()) + list(TDBP_MULTI_SIGNATURES.items()) + \
-            list(RELOCATE_SIGNATURES.items()):
+            list(RELOCATE_SIGNATURES.items()) + list(KTRACK_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
