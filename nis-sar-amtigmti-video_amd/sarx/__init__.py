@@ -23,6 +23,7 @@ from .tdbp_pair_search import TdbpPairSearchResult, tdbp_pair_search
 from .tdbp_multi import TdbpMultiResult, tdbp_multi
 from .relocate import RelocateResult, ground_relocate, reference_geometry, relocate_frames
 from .ktrack import GroundTracker, KalmanTrackParams, KalmanTrackResult, TrackTimeError, ground_track
+from .pga import PgaParams, PgaResult, apply_azimuth_phase, pga
 from .focus import (FocusFuture, ati_dpca, clear_plan_cache, dpca_pulse_shift, focus_ati_dpca, focus_stream, phase_balance,
                     sar_focus_csa, sar_focus_csa_async, two_channel_workspace)
 
@@ -38,4 +39,5 @@ __all__ = ["SarxError", "Context", "CsaPlan", "FocusLanes", "add_noise_rel_dev",
            "tdbp_pair", "TdbpPairResult", "tdbp_pair_search", "TdbpPairSearchResult",
            "tdbp_multi", "TdbpMultiResult",
            "ground_relocate", "reference_geometry", "relocate_frames", "RelocateResult",
-           "ground_track", "GroundTracker", "KalmanTrackParams", "KalmanTrackResult", "TrackTimeError"]
+           "ground_track", "GroundTracker", "KalmanTrackParams", "KalmanTrackResult", "TrackTimeError",
+           "pga", "apply_azimuth_phase", "PgaParams", "PgaResult"]

@@ -494,6 +494,30 @@ KTRACK_SIGNATURES = {
     "sarx_ktrack_run_dev": (_i, [_vp, _P(KtrackParams), _P(KtrackFrame), _i, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp]),
 }
 
+# include/sarx_pga.h: the phase-gradient autofocus, a sixteenth table bound the same way
+PGA_MAX_ITER, PGA_MAX_RG, PGA_MAX_FRAMES = 8, 1 << 20, 65535                  # SARX_PGA_MAX_ITER, _MAX_RG, _MAX_FRAMES
+PGA_SIZES = (64, 128, 256, 512, 1024)
+
+
+class PgaParams(C.Structure):
+    """sarx_pga_params (56 bytes)"""
+    _fields_ = [("n_iter", C.c_int32), ("half_width", C.c_int32 * PGA_MAX_ITER), ("reserved", C.c_int32), ("min_contrast", C.c_double),
+                ("power_floor", C.c_double)]
+
+
+class PgaRecord(C.Structure):
+    """sarx_pga_record (32 bytes)"""
+    _fields_ = [("s2", C.c_double), ("s4", C.c_double), ("rms_phase", C.c_double), ("n_cols_used", C.c_int32),
+                ("n_bins_supported", C.c_int32)]
+
+
+PGA_SIGNATURES = {
+    "sarx_pga_check": (_i, [_P(PgaParams), _i, _i, _sz, _i, _sz]),
+    "sarx_pga_workspace_bytes": (_i, [_P(PgaParams), _i, _i, _sz, _i, _sz, _P(_sz)]),
+    "sarx_pga_dev": (_i, [_vp, _vp, _vp, _i, _i, _sz, _i, _sz, _P(PgaParams), _vp, _vp, _vp]),
+    "sarx_pga_apply_dev": (_i, [_vp, _vp, _vp, _i, _i, _sz, _i, _sz, _vp, _sz, _i]),
+}
+
 _lib = None
 
 
@@ -510,7 +534,7 @@ def load():
             list(BALANCE_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(COHERENCE_SIGNATURES.items()) + list(OSCFAR_SIGNATURES.items()) + \
             list(CLUSTER_SIGNATURES.items()) + list(ATIGATE_SIGNATURES.items()) + list(TDBP_SEARCH_SIGNATURES.items()) + \
             list(TDBP_PAIR_SIGNATURES.items()) + list(TDBP_PAIR_SEARCH_SIGNATURES.items()) + list(TDBP_MULTI_SIGNATURES.items()) + \
-            list(RELOCATE_SIGNATURES.items()) + list(KTRACK_SIGNATURES.items()):
+            list(RELOCATE_SIGNATURES.items()) + list(KTRACK_SIGNATURES.items()) + list(PGA_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

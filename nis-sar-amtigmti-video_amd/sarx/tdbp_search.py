@@ -150,12 +150,16 @@ def tdbp_search(raw_t, pos_plat, vel_plat, t_start, num_samples, vel_hyps, t_pul
 
 
 def tdbp_autofocus(raw_t, pos_plat, vel_plat, t_start, num_samples, t_pulses, scene_size, nx, ny, *, v0, half_span, n,
-                   direction=None, metric="s4", consts=None, ctx=None, d_image=None):
+                   direction=None, metric="s4", consts=None, ctx=None, d_image=None, pga=None, pga_axis=0):
     """One search on the line ``v0 + s * direction`` (n odd hypotheses over +-half_span; direction defaults to the ground
     projection of the mean platform velocity: the along-track direction, the only component sharpness can tell) and one
     ``tdbp_gpu`` at the estimate.  returns (v_est [3], image complex128 [ny x nx], TdbpSearchResult).  v0 carries what is known
     from elsewhere - the radial component above all.  ``d_image`` as in ``tdbp_gpu`` (device input only): the image is left there
-    and None is returned in its place."""
+    and None is returned in its place.  ``pga``: a PgaParams: the frame at the estimate is passed through ``sarx.pga`` (as
+    complex64, azimuth along image axis ``pga_axis``; 1 needs nx and ny to be multiples of 32) before it is returned, which removes
+    what no velocity can: a phase error over the aperture that is not a parabola.  It needs the host image (no ``d_image``)."""
+    if pga is not None and d_image is not None:
+        raise ValueError("pga takes the host image: d_image holds complex128, the autofocus works on complex64")
     if direction is None:
         direction = np.asarray(vel_plat, dtype=np.float64).mean(axis=0) * np.array([1.0, 1.0, 0.0])
     hyps = tdbp_velocity_line(v0, direction, half_span, n)
@@ -163,4 +167,7 @@ def tdbp_autofocus(raw_t, pos_plat, vel_plat, t_start, num_samples, t_pulses, sc
     v_est = res.estimate(metric).velocity
     img = tdbp_gpu(raw_t, pos_plat, vel_plat, t_start, num_samples, v_est, t_pulses, scene_size, nx, ny, consts=consts, ctx=ctx,
                    d_image=d_image)
+    if pga is not None:
+        from .pga import pga as _pga
+        img = _pga(np.asarray(img, dtype=np.complex64), pga, axis=pga_axis, ctx=ctx).image.astype(np.complex128)
     return v_est, img, res
